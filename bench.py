@@ -12,6 +12,7 @@ scatter], 48 B/key) beside it; --path contract swaps the two.  N = 1 sorts BASEL
 uint32 (std::mt19937 raw outputs, seeds 1/2/3 cycled over the K pre-staged batches); --n 1e7 is configs[1], --pairs
 configs[3] (key + payload pairs).  N > 1 sorts N x 10^8 keys sharded by key range (configs[4] at N = 8) through
 vrs_dist_sort_keys_u32: the hybrid sort with the RCCL all-to-all between its two MSD passes.  Rank 0 prints ONE JSON line.
+--dump-outputs DIR (N = 1) writes the arrays the timed path returned in its last step to DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -61,6 +62,25 @@ def pick_dominant(kernels: dict) -> str | None:
         if best_key is None or key > best_key:
             best, best_key = name, key
     return best
+
+
+DUMP_VALUES = 1 << 22  # --dump-outputs: float64 values written in all (32 MiB)
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """--dump-outputs DIR: the arrays the timed path's last step handed its caller, as DIR/<name>.npy in float64 (exact for every
+    uint32).  Arrays longer than their share of DUMP_VALUES are written at one fixed, seeded sample of positions (the same positions
+    for every array of the step and in every run, ascending), so two builds can be compared output for output."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    share = DUMP_VALUES // len(arrays)
+    pos = None if n <= share else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, share, replace=False))
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", (a if pos is None else a[pos]).astype(np.float64))
+    print(f"[bench] --dump-outputs: {', '.join(arrays)} of the last timed step -> {out_dir} "
+          f"({'all' if pos is None else pos.size} of {n} values each)", file=sys.stderr)
 
 
 def mt19937_keys(seed: int, n: int) -> np.ndarray:
@@ -265,6 +285,11 @@ def bench_single(args):
                  if (lambda r: r[0] != 0 or r[1:] != fingerprints[i % len(pristine)])(batches[i].verifyKeys(n))]
     if timed_bad:
         raise SystemExit(f"VERIFICATION FAILED: timed-region outputs of steps {timed_bad} are not sorted permutations of their inputs")
+    if args.dump_outputs:  # the last timed step's output, before the reruns below overwrite it
+        last = np.empty(n, dtype=np.uint32)
+        batches[K - 1].downloadWithStagingBuffer(last)
+        dump_outputs(args.dump_outputs, {"sorted_keys": last})
+        del last
 
     # ---- outside the timed region: (a) the same K steps with no events at all (instrumentation overhead check),
     # (b) once more with every kernel timed, for the per-kernel breakdown
@@ -562,6 +587,12 @@ def bench_pairs(args):
            or vals[i].verifyKeys(n)[1:] != val_print]
     if bad:
         raise SystemExit(f"VERIFICATION FAILED: timed-region outputs of steps {bad}")
+    if args.dump_outputs:  # the last timed step's keys and payloads, before the reruns below overwrite them
+        lk, lv = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        keys[K - 1].downloadWithStagingBuffer(lk)
+        vals[K - 1].downloadWithStagingBuffer(lv)
+        dump_outputs(args.dump_outputs, {"sorted_keys": lk, "sorted_payloads": lv})
+        del lk, lv
     # bit for bit against std::stable_sort (keys AND payloads) for the first batch of every seed; its time is the CPU baseline
     base = None
     exact = None
@@ -1223,7 +1254,7 @@ def other_configs(args):
     import copy
     out = {}
     a1 = copy.copy(args)
-    a1.n, a1.pairs = 10 ** 7, False
+    a1.n, a1.pairs, a1.dump_outputs = 10 ** 7, False, None
     r = bench_single(a1)
     out["configs[1]"] = {"workload": r["config"]["workload"], "path": r["config"]["path"].split(":")[0].split(" --")[0], "value": r["value"],
                          "unit": r["unit"], "ms_per_step": r["ms_per_step"], "steps": r["steps"],
@@ -1234,6 +1265,7 @@ def other_configs(args):
                          "cpu_baseline": r.get("cpu_baseline", {}).get("value")}
     a3 = copy.copy(args)
     a3.n, a3.pairs, a3.steps, a3.exact_seeds = 10 ** 8, True, min(args.steps, 10), 1  # (one seed: its std::stable_sort takes 9 s)
+    a3.dump_outputs = None  # (--dump-outputs is the headline's)
     r = bench_pairs(a3)
     out["configs[3]"] = {"workload": r["config"]["workload"], "path": r["config"]["path"].split(":")[0], "value": r["value"], "unit": r["unit"],
                          "ms_per_step": r["ms_per_step"], "steps": r["steps"], "sort_roofline": r["sort_roofline"],
@@ -1270,7 +1302,15 @@ def main():
     ap.add_argument("--path", choices=["one_call", "contract"], default="one_call",
                     help="N = 1: which path is timed as `value` (the other is reported beside it): the one-call sort "
                          "(one counting read + look-back scatters) or the reference's stage-by-stage contract path")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N = 1: after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy "
+                         "(float64; sorted_keys, with --pairs also sorted_payloads; outputs over 2^22 values in all at a fixed, seeded "
+                         "sample of positions)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.loopback_ranks > 0 or os.environ.get("VRS_BENCH_FORCE_MULTI") == "1"):
+        ap.error("--dump-outputs covers the single-GPU line (N = 1)")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # convenience: re-launch under torch.distributed.run the way the driver does

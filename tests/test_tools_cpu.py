@@ -105,3 +105,24 @@ def test_the_line_describes_the_cut_the_library_runs():
         assert f"up to {cap.value} " in text and f"low {32 - a.value - b.value} bits" in text and f"{scratch.value / 1e6:.0f} MB" in text
         assert ("48 B/pair" in text) == pairs and ("24 B/key" in text) != pairs
     assert "(7 bits)" in bench.pool_path_text(lib, 10 ** 8) and "(8 bits)" not in bench.pool_path_text(lib, 10 ** 8)  # the default cut: 7 + 7
+
+
+def test_bench_dump_outputs_is_exact_bounded_and_repeatable(tmp_path):
+    import numpy as np
+    bench = _load(ROOT / "bench.py", "bench_for_dump")
+    keys = np.sort(bench.mt19937_keys(1, 3 * bench.DUMP_VALUES))
+    pay = np.arange(keys.size, dtype=np.uint32)
+    bench.dump_outputs(tmp_path / "a", {"sorted_keys": keys, "sorted_payloads": pay})
+    bench.dump_outputs(tmp_path / "b", {"sorted_keys": keys, "sorted_payloads": pay})
+    total = 0
+    for name in ("sorted_keys", "sorted_payloads"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.size == bench.DUMP_VALUES // 2 and np.array_equal(a, b)
+        total += (tmp_path / "a" / f"{name}.npy").stat().st_size
+    assert total <= 64 * 10 ** 6
+    # the positions are one ascending sample shared by both arrays: the payloads ARE the positions, and the keys there are exact
+    pos = np.load(tmp_path / "a" / "sorted_payloads.npy").astype(np.int64)
+    assert np.all(np.diff(pos) > 0) and np.array_equal(np.load(tmp_path / "a" / "sorted_keys.npy"), keys[pos].astype(np.float64))
+    # a short output goes out whole
+    bench.dump_outputs(tmp_path / "c", {"sorted_keys": keys[:1000]})
+    assert np.array_equal(np.load(tmp_path / "c" / "sorted_keys.npy"), keys[:1000].astype(np.float64))

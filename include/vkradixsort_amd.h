@@ -292,6 +292,43 @@ int vrs_msd_finish_ticket(vrs_context ctx, uint32_t *ticket);
 int vrs_msd_finish_status_at(vrs_context ctx, uint32_t ticket, int *took);
 
 /*
+ * Segmented sorts (build extension; no reference counterpart -- the reference's callers sort per-tile or per-cell lists one
+ * dispatch at a time): many independent segments of one buffer sorted by one call.  offsets: a device buffer of num_segments + 1
+ * uint32; segment i = keys[offsets[i], offsets[i+1]).  Every segment ends up ascending in `keys` (and `values`); the pairs form is
+ * stable (each segment == std::stable_sort by key), bare keys == std::sort.  Elements outside [offsets[0], offsets[num_segments])
+ * and gaps no segment covers are not touched.  keys_tmp / values_tmp hold num_elements entries and are scratch.
+ * num_elements == 0 or num_segments == 0: VRS_OK, nothing done.  NULL handles, buffers of fewer than 4 * num_elements bytes and an
+ * offsets buffer of fewer than 4 * (num_segments + 1) bytes: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Malformed
+ * offsets never cause an access out of bounds: the kernels clamp each segment to [min(b, n), min(max(b, e), n)) with the function
+ * vrs_segment_tier_for exports; what overlapping clamped ranges hold afterwards is unspecified.
+ * Tiers by segment length (VRS_SEGMENT_*): one wave per segment up to 1789 elements, one workgroup sorting inside LDS up to 14333
+ * keys / 13312 pairs (both read and write each segment once: 8 bytes per key, 16 per pair), one workgroup per segment sorting through
+ * keys_tmp below VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS, and from there on the one-call sort (vrs_sort_keys_u32 / vrs_sort_pairs_u32) on
+ * views of the buffers.  Blocking: below VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS elements in all (no segment can reach the one-call tier)
+ * the call only enqueues; otherwise it waits (bounded by VRS_TUNE_PLAN_WAIT_MS) until the classification of the segments has reached
+ * pinned host memory -- never for the sorts -- and enqueues the one-call sorts.  A pending one-call sort is settled first.
+ * int32 / float32 keys: vrs_transform_keys before and after.
+ */
+typedef enum vrs_segment_tier {
+    VRS_SEGMENT_WAVE = 0,    /* up to 1789 elements (segments of 0 or 1 element are counted here and never touched) */
+    VRS_SEGMENT_BLOCK = 1,   /* up to 14333 keys / 13312 pairs */
+    VRS_SEGMENT_GLOBAL = 2,  /* longer, below VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS */
+    VRS_SEGMENT_ONE_CALL = 3 /* from VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS on */
+} vrs_segment_tier;
+/* offsets: device buffer of num_segments + 1 uint32; segment i = keys[offsets[i], offsets[i+1]). */
+int vrs_sort_segments_u32(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, uint32_t num_elements,
+                          vrs_buffer offsets, uint32_t num_segments);
+int vrs_sort_segments_pairs_u32(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values,
+                                vrs_buffer values_tmp, uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments);
+/* cumulative per context: segments sorted by each tier (waits for the context's stream; any pointer may be NULL) */
+int vrs_segmented_stats(vrs_context ctx, uint64_t *wave_segments, uint64_t *block_segments,
+                        uint64_t *global_segments, uint64_t *one_call_segments);
+/* the classification both the device and the tests use: a pure function, needs no device.  pairs != 0: key + payload pairs;
+ * one_call_min_keys: VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS (0 = never the one-call tier); *tier = VRS_SEGMENT_*. */
+int vrs_segment_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, int pairs, uint32_t one_call_min_keys,
+                         int *tier, uint32_t *clamped_begin, uint32_t *clamped_end);
+
+/*
  * Key preprocessing the reference leaves to the integrator ("you have to preprocess negative numbers",
  * README.md:154-155): in-place, order-preserving maps between int32 / float32 bit patterns and the uint32
  * keys the sort orders.  Asynchronous.  Apply *_TO_SORTABLE before the four passes and the inverse after.
@@ -604,6 +641,9 @@ typedef enum vrs_tuning_key {
                                      are sorted: 43 instead of 70 KB of LDS, three workgroups per CU instead of two.  5-9 % faster from 2.6e7 to 8e7
                                      pairs; level at 10^8 and 2e8 (buckets of 12-13 rows), where the form that carries the payloads through both
                                      passes stays (profiles/labs/r06_pairs_packed.txt) */
+    VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS = 27, /* the segmented sorts hand a segment of this many elements or more to the one-call sort
+                                       (vrs_sort_keys_u32 / vrs_sort_pairs_u32 on views); shorter ones beyond the LDS tiers are sorted by one
+                                       workgroup each.  0 = never.  Default 2^20 */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

@@ -71,6 +71,12 @@ VRS_TUNE_MSD_POOL_PAIRS = 23
 VRS_TUNE_MSD_POOL_TOP_BITS = 24
 VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25
 VRS_TUNE_MSD_POOL_PAIRS_PACKED = 26
+VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS = 27
+SEGMENT_ONE_CALL_MIN_KEYS_DEFAULT = 1 << 20  # the library's default for VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS
+# tiers of the segmented sorts (vrs_segment_tier) and the lengths that bound them
+VRS_SEGMENT_WAVE, VRS_SEGMENT_BLOCK, VRS_SEGMENT_GLOBAL, VRS_SEGMENT_ONE_CALL = 0, 1, 2, 3
+SEGMENT_WAVE_MAX = 1789
+SEGMENT_BLOCK_MAX_KEYS, SEGMENT_BLOCK_MAX_PAIRS = 14333, 13312
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -194,6 +200,10 @@ _SIGNATURES = [
     ("vrs_debug_atomic_rank_selftest", c_int, [c_void_p, c_uint32, c_uint32, POINTER(c_uint64)]),
     ("vrs_rank_mode", c_int, [c_void_p]),
     ("vrs_set_tuning", c_int, [c_void_p, c_int, c_int]),
+    ("vrs_sort_segments_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+    ("vrs_sort_segments_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+    ("vrs_segmented_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_segment_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -23,6 +23,8 @@
 
 #include "vrs_kernels.h"
 
+struct vrs_segmented_state;  // vrs_capi_segmented.hip
+
 struct vrs_context_t {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -162,6 +164,9 @@ struct vrs_context_t {
     } one_read;
     bool one_read_settling = false;
     uint32_t os_msd_half_stamp = 0;      // stamp of the most recent vrs_msd_finish_u32's plan
+    // segmented sorts (vrs_capi_segmented.hip)
+    vrs_segmented_state *seg = nullptr;
+    uint32_t seg_one_call_min_keys = 1u << 20;  // VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS
 };
 
 struct vrs_buffer_t {
@@ -236,6 +241,7 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g);
 int one_read_complete(vrs_context ctx, bool *done);
 int one_read_settle(vrs_context ctx);
 int settle_pending(vrs_context ctx);
+void segmented_release(vrs_context ctx);
 int sort_one_read(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values, vrs_buffer values_tmp,
                          uint32_t n, int key_bytes, uint32_t key_base);
 int sort_all_passes(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values,

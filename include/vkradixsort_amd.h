@@ -329,6 +329,46 @@ int vrs_segment_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, in
                          int *tier, uint32_t *clamped_begin, uint32_t *clamped_end);
 
 /*
+ * Top-k selection (build extension; no reference counterpart): the k smallest (or largest) keys of every segment of one buffer and
+ * where they sat, by radix select, in one call.  offsets: a device buffer of num_segments + 1 uint32; segment i is
+ * keys[offsets[i], offsets[i+1]) clamped exactly as vrs_segment_tier_for clamps it.  key_type (vrs_topk_key_type) fixes the rank of
+ * a key x: r(x) = x (U32), x ^ 0x80000000 (I32), the VRS_KEYS_FLOAT32_TO_SORTABLE map (F32, IEEE-754 total order); VRS_TOPK_LARGEST
+ * ranks by ~r(x).  The map is applied as the keys are read; `keys` and `offsets` are never written.
+ * Segment i of length L and m = min(k, L): its selected set is the first m positions of the STABLE ascending order of r over the
+ * segment (smallest r first; equal keys lowest index first).  out_keys[i*k + j] (j < m) holds a selected key's bit pattern and
+ * out_indices[i*k + j] its position relative to the clamped begin; with VRS_TOPK_SORTED slot j holds the j-th entry of the stable
+ * order, without it the same m entries in some order.  Slots j in [m, k) of both arrays get 0xFFFFFFFF.  out_indices may be NULL.
+ * Bytes of the out buffers past 4 * num_segments * k are never written.  scratch: at least vrs_topk_scratch_bytes(...) bytes (at
+ * most 4 n + 16 S k + 1 MiB), contents afterwards unspecified; given that much the call never fails for lack of memory.
+ * k == 0 or num_segments == 0: VRS_OK, nothing done.  NULL handles other than out_indices, an unknown key_type or flag bit,
+ * num_segments * k >= 2^32 and undersized buffers: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
+ * Tiers by clamped length (vrs_topk_tier): up to 8192 keys one workgroup per segment selects inside LDS; longer segments are streamed
+ * by one workgroup each; from VRS_TUNE_TOPK_GRID_MIN_KEYS on every phase is one launch over all the grid tier's segments.  Stream-
+ * ordered on the context's stream; the call only enqueues (after settling a pending one-call sort) -- except with VRS_TOPK_SORTED and
+ * k > 4096, where the survivors are sorted by vrs_sort_segments_pairs_u32 (vrs_sort_segments_u32 without out_indices), which may wait
+ * for the stream when its work lists grow; that sort's segments count in vrs_segmented_stats.
+ */
+typedef enum vrs_topk_key_type { VRS_TOPK_U32 = 0, VRS_TOPK_I32 = 1, VRS_TOPK_F32 = 2 } vrs_topk_key_type;
+enum { VRS_TOPK_LARGEST = 1, VRS_TOPK_SORTED = 2 }; /* flags */
+typedef enum vrs_topk_tier {
+    VRS_TOPK_LDS = 0,   /* up to 8192 keys (empty segments included) */
+    VRS_TOPK_BLOCK = 1, /* longer, below VRS_TUNE_TOPK_GRID_MIN_KEYS */
+    VRS_TOPK_GRID = 2   /* from VRS_TUNE_TOPK_GRID_MIN_KEYS on */
+} vrs_topk_tier;
+int vrs_topk_segments(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments,
+                      uint32_t k, int key_type, int flags, vrs_buffer out_keys, vrs_buffer out_indices /* may be NULL */,
+                      vrs_buffer scratch);
+/* the scratch vrs_topk_segments needs: a pure function, needs no device (0 for k == 0 or num_segments == 0) */
+int vrs_topk_scratch_bytes(uint32_t num_elements, uint32_t num_segments, uint32_t k, int flags, uint64_t *bytes);
+/* the classification both the device and the tests use: a pure function, needs no device.  grid_min_keys: VRS_TUNE_TOPK_GRID_MIN_KEYS
+ * (0 = never the grid tier); *tier = VRS_TOPK_*. */
+int vrs_topk_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, uint32_t grid_min_keys,
+                      int *tier, uint32_t *clamped_begin, uint32_t *clamped_end);
+/* cumulative per context: segments each tier was given by the classification (waits for the context's stream; any pointer may be
+ * NULL).  Grid-tier segments beyond 4096 in one call -- only overlapping ranges get there -- count as grid and run in the BLOCK kernel. */
+int vrs_topk_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments);
+
+/*
  * Key preprocessing the reference leaves to the integrator ("you have to preprocess negative numbers",
  * README.md:154-155): in-place, order-preserving maps between int32 / float32 bit patterns and the uint32
  * keys the sort orders.  Asynchronous.  Apply *_TO_SORTABLE before the four passes and the inverse after.
@@ -644,6 +684,9 @@ typedef enum vrs_tuning_key {
     VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS = 27, /* the segmented sorts hand a segment of this many elements or more to the one-call sort
                                        (vrs_sort_keys_u32 / vrs_sort_pairs_u32 on views); shorter ones beyond the LDS tiers are sorted by one
                                        workgroup each.  0 = never.  Default 2^20 */
+    VRS_TUNE_TOPK_GRID_MIN_KEYS = 28, /* top-k: segments of this many keys or more take the grid tier (every phase one launch over all of
+                                       them); shorter ones beyond the LDS tier are streamed by one workgroup each.  0 = never.  Default 2^17 (the measured
+                                       crossover, DESIGN "K7") */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

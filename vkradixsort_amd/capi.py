@@ -77,6 +77,14 @@ SEGMENT_ONE_CALL_MIN_KEYS_DEFAULT = 1 << 20  # the library's default for VRS_TUN
 VRS_SEGMENT_WAVE, VRS_SEGMENT_BLOCK, VRS_SEGMENT_GLOBAL, VRS_SEGMENT_ONE_CALL = 0, 1, 2, 3
 SEGMENT_WAVE_MAX = 1789
 SEGMENT_BLOCK_MAX_KEYS, SEGMENT_BLOCK_MAX_PAIRS = 14333, 13312
+VRS_TUNE_TOPK_GRID_MIN_KEYS = 28
+TOPK_GRID_MIN_KEYS_DEFAULT = 1 << 17  # the library's default for VRS_TUNE_TOPK_GRID_MIN_KEYS
+# top-k selection: key types, flags, tiers (vrs_topk_tier) and the lengths that bound them
+VRS_TOPK_U32, VRS_TOPK_I32, VRS_TOPK_F32 = 0, 1, 2
+VRS_TOPK_LARGEST, VRS_TOPK_SORTED = 1, 2
+VRS_TOPK_LDS, VRS_TOPK_BLOCK, VRS_TOPK_GRID = 0, 1, 2
+TOPK_LDS_MAX = 8192
+TOPK_SORT_IN_LDS_MAX_K = 4096  # VRS_TOPK_SORTED beyond this k sorts the survivors with vrs_sort_segments_pairs_u32
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -204,6 +212,10 @@ _SIGNATURES = [
     ("vrs_sort_segments_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
     ("vrs_segmented_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_segment_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+    ("vrs_topk_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+    ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+    ("vrs_topk_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]

@@ -279,6 +279,7 @@ int vrs_context_destroy(vrs_context ctx) {
     if (ctx->os_msd_plan) (void)hipFree(ctx->os_msd_plan);
     if (ctx->os_plan_a) (void)hipFree(ctx->os_plan_a);
     segmented_release(ctx);
+    topk_release(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return VRS_OK;
@@ -685,6 +686,10 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
         case VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS:
             if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the segmented sorts' one-call threshold must be >= 0");
             ctx->seg_one_call_min_keys = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_TOPK_GRID_MIN_KEYS:
+            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the top-k grid tier's threshold must be >= 0");
+            ctx->topk_grid_min_keys = static_cast<uint32_t>(value);
             return VRS_OK;
         case VRS_TUNE_MSD_POOL_PAIRS_PACKED:
             if (value < -1 || value > 1) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pairs' packed local sort: -1 (by size), 0 (never) or 1 (always)");

@@ -24,6 +24,7 @@
 #include "vrs_kernels.h"
 
 struct vrs_segmented_state;  // vrs_capi_segmented.hip
+struct vrs_topk_state;       // vrs_capi_topk.hip
 
 struct vrs_context_t {
     int device = 0;
@@ -167,6 +168,9 @@ struct vrs_context_t {
     // segmented sorts (vrs_capi_segmented.hip)
     vrs_segmented_state *seg = nullptr;
     uint32_t seg_one_call_min_keys = 1u << 20;  // VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS
+    // top-k selection (vrs_capi_topk.hip)
+    vrs_topk_state *topk = nullptr;
+    uint32_t topk_grid_min_keys = 1u << 17;  // VRS_TUNE_TOPK_GRID_MIN_KEYS (vrs::kTopkDefaultGridMinKeys)
 };
 
 struct vrs_buffer_t {
@@ -242,6 +246,7 @@ int one_read_complete(vrs_context ctx, bool *done);
 int one_read_settle(vrs_context ctx);
 int settle_pending(vrs_context ctx);
 void segmented_release(vrs_context ctx);
+void topk_release(vrs_context ctx);
 int sort_one_read(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values, vrs_buffer values_tmp,
                          uint32_t n, int key_bytes, uint32_t key_base);
 int sort_all_passes(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values,

@@ -1,0 +1,612 @@
+// vrs_topk.hip -- top-k selection (vrs_topk_segments): the k smallest (or largest) keys of every segment by radix select, one sequence
+// of launches whose shapes do not depend on the segments.
+//   classify: one thread per segment; its tier (topk_tier, the function vrs_topk_tier_for exports), a place on the LDS tier's list (front
+//     of one array) or the BLOCK tier's (back of it), or a grid slot with a range of tiles; per-tier counters for vrs_topk_stats.
+//   selection: digits of 11, 11 and 10 bits of the rank r from the top.  A level counts the digit of every key whose higher bits match
+//     the prefix chosen so far, picks the digit d* that holds the need-th key, and stops early once every matching key is needed.
+//   emission: in index order -- keys below the prefix to slots [0, lt), the first `need` keys equal to it (lowest index first) to
+//     [lt, m) -- so a stable sort by r of the m survivors is the stable order (equal keys stay in index order, and the two groups occupy
+//     disjoint ranges of r).
+//   LDS tier (up to kTopkLdsCap keys): one 256-thread workgroup per segment, ranks read once into LDS.
+//   BLOCK tier: one 1024-thread workgroup per segment streaming 16384-key tiles: one read per level and one for the emission.
+//   GRID tier: each phase one launch over a fixed grid that walks the tiles of every grid slot; per-workgroup LDS histograms flushed with
+//     one atomic per non-zero bin, one workgroup per slot picks the digit, a counting read and a per-slot scan order the emission.
+//   sorted output (k <= kTopkSortCap): one workgroup per segment sorts its survivors in LDS (local_pass, stable, over the bits that vary).
+#include "vrs_topk.hpp"
+
+#include "vrs_local_sort.hpp"
+
+namespace vrs {
+namespace {
+
+__device__ __forceinline__ bool sel_less(uint32_t r, const TopkSel &s) { return s.shift < 32u && (r >> s.shift) < (s.prefix >> s.shift); }
+__device__ __forceinline__ bool sel_match(uint32_t r, const TopkSel &s) { return s.shift >= 32u || (r >> s.shift) == (s.prefix >> s.shift); }
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+}
+
+// counts digit d of the calling lane; one add for the whole instruction when every active lane has the same digit (equal keys)
+__device__ __forceinline__ void hist_add(uint32_t *s_hist, uint32_t d) {
+    const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
+    const uint64_t active = __ballot(1);
+    if (__ballot(d == d0) == active) {
+        if (lanes_below(active) == 0u) atomicAdd(&s_hist[d0], static_cast<uint32_t>(__popcll(active)));
+    } else {
+        atomicAdd(&s_hist[d], 1u);
+    }
+}
+
+// the digit histogram (level `level`) of the keys of one tile that match the selection so far; position p of the tile: load(p)
+template <int THREADS, int ITEMS, class Load>
+__device__ __forceinline__ void hist_tile(Load load, uint32_t cnt, const TopkSel &sel, int level, uint32_t *s_hist) {
+    const uint32_t shift = topk_level_shift(level), mask = topk_level_mask(level);
+    uint32_t r[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = i * THREADS + threadIdx.x;
+        r[i] = p < cnt ? load(p) : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = i * THREADS + threadIdx.x;
+        if (p < cnt && sel_match(r[i], sel)) hist_add(s_hist, (r[i] >> shift) & mask);
+    }
+}
+
+// Picks the digit that holds the need-th matching key (1 <= need <= keys counted): s_res = {d*, keys below it, keys at it}.
+template <int THREADS>
+__device__ __forceinline__ void select_digit(const uint32_t *s_hist, uint32_t need, uint32_t *s_wtot, uint32_t *s_res) {
+    constexpr int PER = kTopkBins / THREADS, WAVES = THREADS / 64;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t c[PER], sum = 0;
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+        c[p] = s_hist[tid * PER + p];
+        sum += c[p];
+    }
+    uint32_t incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o);
+        if (lane >= static_cast<uint32_t>(o)) incl += t;
+    }
+    if (lane == 63u) s_wtot[wave] = incl;
+    __syncthreads();
+    uint32_t excl = incl - sum;
+#pragma unroll
+    for (int v = 0; v < WAVES; ++v) excl += static_cast<uint32_t>(v) < wave ? s_wtot[v] : 0u;
+    if (excl < need && need <= excl + sum) {  // exactly one thread
+        uint32_t acc = excl;
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            if (acc + c[p] >= need) {
+                s_res[0] = tid * PER + p;
+                s_res[1] = acc;
+                s_res[2] = c[p];
+                break;
+            }
+            acc += c[p];
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ void sel_apply(TopkSel &sel, int level, uint32_t d, uint32_t below, uint32_t at) {
+    sel.lt += below;
+    sel.need -= below;
+    sel.shift = topk_level_shift(level);
+    sel.prefix |= d << sel.shift;
+    sel.done = (at == sel.need || level == kTopkLevels - 1) ? 1u : 0u;
+}
+
+// Emits one tile in index order (position p = i * THREADS + tid; index of p: pos0 + p).  lt_base / eq_base: keys below / equal to the
+// prefix in the segment's tiles before this one.  Returns this tile's two counts.
+template <int THREADS, int ITEMS, class Load>
+__device__ __forceinline__ uint2 emit_tile(Load load, uint32_t cnt, uint32_t pos0, const TopkSel &sel, uint32_t m, uint32_t lt_base,
+                                           uint32_t eq_base, uint32_t *ok, uint32_t *oi, int key_type, bool largest, uint32_t *s_scan,
+                                           uint32_t *s_wtot) {
+    constexpr int WAVES = THREADS / 64, E = ITEMS * WAVES;
+    static_assert(E % 64 == 0 && E <= THREADS, "one scanning thread per (item, wave)");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t r[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = i * THREADS + tid;
+        r[i] = p < cnt ? load(p) : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = i * THREADS + tid;
+        const bool lt = p < cnt && sel_less(r[i], sel), eq = p < cnt && !lt && sel_match(r[i], sel);
+        const uint64_t bl = __ballot(lt), be = __ballot(eq);
+        if (lane == 0u) {
+            s_scan[i * WAVES + wave] = static_cast<uint32_t>(__popcll(bl));
+            s_scan[E + i * WAVES + wave] = static_cast<uint32_t>(__popcll(be));
+        }
+    }
+    __syncthreads();
+    if (tid < static_cast<uint32_t>(E)) {
+        const uint32_t a = s_scan[tid], b = s_scan[E + tid];
+        uint32_t ia = a, ib = b;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t ta = __shfl_up(ia, o), tb = __shfl_up(ib, o);
+            if (lane >= static_cast<uint32_t>(o)) {
+                ia += ta;
+                ib += tb;
+            }
+        }
+        if (lane == 63u) {
+            s_wtot[wave] = ia;
+            s_wtot[8 + wave] = ib;
+        }
+        s_scan[tid] = ia - a;
+        s_scan[E + tid] = ib - b;
+    }
+    __syncthreads();
+    if (tid < static_cast<uint32_t>(E)) {
+        uint32_t add_a = 0, add_b = 0;
+        for (uint32_t v = 0; v < wave; ++v) {
+            add_a += s_wtot[v];
+            add_b += s_wtot[8 + v];
+        }
+        s_scan[tid] += add_a;
+        s_scan[E + tid] += add_b;
+    }
+    __syncthreads();
+    uint2 tot = make_uint2(0u, 0u);
+#pragma unroll
+    for (int v = 0; v < E / 64; ++v) {
+        tot.x += s_wtot[v];
+        tot.y += s_wtot[8 + v];
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = i * THREADS + tid;
+        const bool lt = p < cnt && sel_less(r[i], sel), eq = p < cnt && !lt && sel_match(r[i], sel);
+        const uint64_t bl = __ballot(lt), be = __ballot(eq);
+        uint32_t slot = 0xFFFFFFFFu;
+        if (lt) {
+            slot = lt_base + s_scan[i * WAVES + wave] + lanes_below(bl);
+            if (slot >= sel.lt) slot = 0xFFFFFFFFu;
+        } else if (eq) {
+            const uint32_t er = eq_base + s_scan[E + i * WAVES + wave] + lanes_below(be);
+            if (er < sel.need) slot = sel.lt + er;
+        }
+        if (slot < m) {
+            ok[slot] = topk_unrank(r[i], key_type, largest);
+            if (oi) oi[slot] = pos0 + p;
+        }
+    }
+    __syncthreads();  // (s_scan and s_wtot are free again)
+    return tot;
+}
+
+__device__ __forceinline__ void fill_tail(uint32_t *ok, uint32_t *oi, uint32_t m, uint32_t k, uint32_t threads) {
+    for (uint32_t j = m + threadIdx.x; j < k; j += threads) {
+        ok[j] = 0xFFFFFFFFu;
+        if (oi) oi[j] = 0xFFFFFFFFu;
+    }
+}
+
+__global__ __launch_bounds__(256) void topk_classify_kernel(TopkArgs a, TopkControl *__restrict__ ctl, uint32_t *__restrict__ list,
+                                                            TopkSlot *__restrict__ slots, uint32_t slot_cap, uint32_t tile_cap) {
+    __shared__ uint32_t s_stat[3];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 3u) s_stat[tid] = 0u;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + tid;
+    if (i < a.num_segments) {
+        uint32_t cb, ce;
+        int tier = topk_tier(a.offsets[i], a.offsets[i + 1u], a.n, a.grid_min_keys, &cb, &ce);
+        atomicAdd(&s_stat[tier], 1u);
+        const uint32_t len = ce - cb, m = min(a.k, len);
+        if (tier == kTopkTierGrid) {
+            const uint32_t tiles = (len + kTopkTile - 1u) / kTopkTile;
+            const unsigned long long old = atomicAdd(&ctl->grid_packed, (static_cast<unsigned long long>(tiles) << 32) | 1ull);
+            const uint32_t slot = static_cast<uint32_t>(old), base = static_cast<uint32_t>(old >> 32);
+            bool valid = false;
+            if (slot < slot_cap) {  // (beyond the caps: overlapping ranges; the BLOCK kernel takes them)
+                valid = static_cast<uint64_t>(base) + tiles <= tile_cap;
+                TopkSlot s{};
+                s.seg = i;
+                s.b = cb;
+                s.len = len;
+                s.m = m;
+                s.tile_base = base;
+                s.tiles = tiles;
+                s.valid = valid ? 1u : 0u;
+                s.sel = topk_sel_init(len, m);
+                slots[slot] = s;
+            }
+            if (!valid) tier = kTopkTierBlock;
+        }
+        if (tier == kTopkTierLds) list[atomicAdd(&ctl->lds_count, 1u)] = i;
+        else if (tier == kTopkTierBlock) list[a.num_segments - 1u - atomicAdd(&ctl->block_count, 1u)] = i;
+    }
+    __syncthreads();
+    if (tid < 3u && s_stat[tid] != 0u) atomicAdd(&a.stats[tid], static_cast<unsigned long long>(s_stat[tid]));
+}
+
+// LDS and BLOCK tiers: one workgroup per listed segment (the workgroups walk the list).  LDS: the ranks are read once into LDS.
+template <int THREADS, int ITEMS, bool LDS>
+__global__ __launch_bounds__(THREADS) void topk_workgroup_kernel(TopkArgs a, const TopkControl *__restrict__ ctl, const uint32_t *__restrict__ list) {
+    constexpr int TILE = THREADS * ITEMS, E = ITEMS * (THREADS / 64);
+    static_assert(!LDS || TILE == static_cast<int>(kTopkLdsCap), "the LDS tier's segment is one tile");
+    __shared__ uint32_t s_hist[kTopkBins];
+    __shared__ uint32_t s_r[LDS ? kTopkLdsCap : 1];
+    __shared__ uint32_t s_scan[2 * E];
+    __shared__ uint32_t s_wtot[16];
+    __shared__ uint32_t s_res[3];
+    const uint32_t count = LDS ? ctl->lds_count : ctl->block_count;
+    const bool largest = (a.flags & kTopkLargest) != 0;
+    const int kt = a.key_type;
+    for (uint32_t j = blockIdx.x; j < count; j += gridDim.x) {
+        const uint32_t seg = LDS ? list[j] : list[a.num_segments - 1u - j];
+        uint32_t b, e;
+        (void)topk_tier(a.offsets[seg], a.offsets[seg + 1u], a.n, 0u, &b, &e);
+        const uint32_t len = e - b, m = min(a.k, len);
+        uint32_t *ok = a.out_keys + static_cast<size_t>(seg) * a.k;
+        uint32_t *oi = a.out_indices ? a.out_indices + static_cast<size_t>(seg) * a.k : nullptr;
+        fill_tail(ok, oi, m, a.k, THREADS);
+        if (m == 0u) continue;
+        const uint32_t *src = a.keys + b;
+        if constexpr (LDS) {
+            for (uint32_t p = threadIdx.x; p < len; p += THREADS) s_r[p] = topk_rank(src[p], kt, largest);
+            __syncthreads();
+        }
+        TopkSel sel = topk_sel_init(len, m);
+        for (int level = 0; level < kTopkLevels && !sel.done; ++level) {
+            for (uint32_t c = threadIdx.x; c < kTopkBins; c += THREADS) s_hist[c] = 0u;
+            __syncthreads();
+            for (uint32_t t0 = 0; t0 < len; t0 += TILE) {
+                const uint32_t cnt = min(static_cast<uint32_t>(TILE), len - t0);
+                if constexpr (LDS) hist_tile<THREADS, ITEMS>([&](uint32_t p) { return s_r[t0 + p]; }, cnt, sel, level, s_hist);
+                else hist_tile<THREADS, ITEMS>([&](uint32_t p) { return topk_rank(src[t0 + p], kt, largest); }, cnt, sel, level, s_hist);
+            }
+            __syncthreads();
+            select_digit<THREADS>(s_hist, sel.need, s_wtot, s_res);
+            sel_apply(sel, level, s_res[0], s_res[1], s_res[2]);
+            __syncthreads();
+        }
+        uint32_t lt_base = 0, eq_base = 0;
+        for (uint32_t t0 = 0; t0 < len; t0 += TILE) {
+            const uint32_t cnt = min(static_cast<uint32_t>(TILE), len - t0);
+            uint2 tot;
+            if constexpr (LDS)
+                tot = emit_tile<THREADS, ITEMS>([&](uint32_t p) { return s_r[t0 + p]; }, cnt, t0, sel, m, lt_base, eq_base, ok, oi, kt, largest, s_scan,
+                                                s_wtot);
+            else
+                tot = emit_tile<THREADS, ITEMS>([&](uint32_t p) { return topk_rank(src[t0 + p], kt, largest); }, cnt, t0, sel, m, lt_base, eq_base, ok,
+                                                oi, kt, largest, s_scan, s_wtot);
+            lt_base += tot.x;
+            eq_base += tot.y;
+        }
+    }
+}
+
+// ---- GRID tier: kernels that walk the virtual tiles [0, tiles taken) of every slot ----
+constexpr int kGridThreads = 1024, kGridItems = 16;
+static_assert(kGridThreads * kGridItems == static_cast<int>(kTopkTile), "a grid tile is one pass of a workgroup");
+
+__device__ __forceinline__ uint32_t grid_slots(const TopkControl *ctl, uint32_t slot_cap) {
+    return min(static_cast<uint32_t>(ctl->grid_packed), slot_cap);
+}
+__device__ __forceinline__ uint32_t grid_tiles(const TopkControl *ctl, uint32_t slot_cap, uint32_t tile_cap) {
+    const uint32_t ns = grid_slots(ctl, slot_cap);
+    return ns == 0u ? 0u : min(static_cast<uint32_t>(ctl->grid_packed >> 32), tile_cap);
+}
+// the slot whose tiles hold virtual tile t: the last slot with tile_base <= t (tile bases grow with the slot)
+__device__ __forceinline__ uint32_t find_slot(const TopkSlot *slots, uint32_t ns, uint32_t t) {
+    uint32_t lo = 0, hi = ns;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) / 2u;
+        if (slots[mid].tile_base <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void topk_grid_init_kernel(const TopkControl *__restrict__ ctl, uint32_t *__restrict__ hist, uint32_t slot_cap) {
+    const uint32_t ns = grid_slots(ctl, slot_cap);
+    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x)
+        for (uint32_t c = threadIdx.x; c < kTopkBins; c += 256u) hist[static_cast<size_t>(s) * kTopkBins + c] = 0u;
+}
+
+// PHASE 0: digit histograms of level `level`; 1: per-tile counts of the two classes; 2: the emission
+template <int PHASE>
+__global__ __launch_bounds__(kGridThreads) void topk_grid_walk_kernel(TopkArgs a, const TopkControl *__restrict__ ctl, const TopkSlot *__restrict__ slots,
+                                                                      uint32_t *__restrict__ hist, uint2 *__restrict__ tilecnt, uint32_t slot_cap,
+                                                                      uint32_t tile_cap, int level) {
+    constexpr int E = kGridItems * (kGridThreads / 64);
+    __shared__ uint32_t s_hist[PHASE == 0 ? kTopkBins : 1];
+    __shared__ uint32_t s_scan[PHASE == 2 ? 2 * E : 1];
+    __shared__ uint32_t s_wtot[16];
+    __shared__ uint32_t s_slot, s_cnt[2];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t ns = grid_slots(ctl, slot_cap), total = grid_tiles(ctl, slot_cap, tile_cap);
+    const bool largest = (a.flags & kTopkLargest) != 0;
+    const int kt = a.key_type;
+    if constexpr (PHASE == 0)
+        for (uint32_t c = tid; c < kTopkBins; c += kGridThreads) s_hist[c] = 0u;
+    uint32_t cur = 0xFFFFFFFFu;
+    bool dirty = false;
+    auto flush = [&]() {  // the workgroup's histogram of slot `cur` into the slot's: one atomic per non-zero bin
+        __syncthreads();
+        for (uint32_t c = tid; c < kTopkBins; c += kGridThreads) {
+            const uint32_t v = s_hist[c];
+            if (v != 0u) {
+                atomicAdd(&hist[static_cast<size_t>(cur) * kTopkBins + c], v);
+                s_hist[c] = 0u;
+            }
+        }
+        __syncthreads();
+    };
+    for (uint32_t t = blockIdx.x; t < total; t += gridDim.x) {
+        if (tid == 0u) s_slot = find_slot(slots, ns, t);
+        __syncthreads();
+        const uint32_t s = s_slot;
+        __syncthreads();
+        if constexpr (PHASE == 0) {
+            if (s != cur) {
+                if (dirty) {
+                    if constexpr (PHASE == 0) flush();
+                    dirty = false;
+                }
+                cur = s;
+            }
+        }
+        const TopkSlot &sl = slots[s];
+        const TopkSel sel = sl.sel;
+        if (!sl.valid || t - sl.tile_base >= sl.tiles) continue;
+        const uint32_t off = (t - sl.tile_base) * kTopkTile, cnt = min(kTopkTile, sl.len - off);
+        const uint32_t *src = a.keys + sl.b + off;
+        auto load = [&](uint32_t p) { return topk_rank(src[p], kt, largest); };
+        if constexpr (PHASE == 0) {
+            if (sel.done) continue;
+            hist_tile<kGridThreads, kGridItems>(load, cnt, sel, level, s_hist);
+            dirty = true;
+        } else if constexpr (PHASE == 1) {
+            if (tid < 2u) s_cnt[tid] = 0u;
+            __syncthreads();
+            uint32_t r[kGridItems];
+#pragma unroll
+            for (int i = 0; i < kGridItems; ++i) {
+                const uint32_t p = i * kGridThreads + tid;
+                r[i] = p < cnt ? load(p) : 0u;
+            }
+            uint32_t nl = 0, ne = 0;
+#pragma unroll
+            for (int i = 0; i < kGridItems; ++i) {
+                const uint32_t p = i * kGridThreads + tid;
+                const bool lt = p < cnt && sel_less(r[i], sel), eq = p < cnt && !lt && sel_match(r[i], sel);
+                nl += static_cast<uint32_t>(__popcll(__ballot(lt)));
+                ne += static_cast<uint32_t>(__popcll(__ballot(eq)));
+            }
+            if ((tid & 63u) == 0u) {
+                atomicAdd(&s_cnt[0], nl);
+                atomicAdd(&s_cnt[1], ne);
+            }
+            __syncthreads();
+            if (tid == 0u) tilecnt[t] = make_uint2(s_cnt[0], s_cnt[1]);
+            __syncthreads();
+        } else {
+            const uint2 base = tilecnt[t];
+            uint32_t *ok = a.out_keys + static_cast<size_t>(sl.seg) * a.k;
+            uint32_t *oi = a.out_indices ? a.out_indices + static_cast<size_t>(sl.seg) * a.k : nullptr;
+            (void)emit_tile<kGridThreads, kGridItems>(load, cnt, off, sel, sl.m, base.x, base.y, ok, oi, kt, largest, s_scan, s_wtot);
+        }
+    }
+    if constexpr (PHASE == 0)
+        if (dirty) flush();
+}
+
+// one workgroup per slot: the digit of level `level` from the slot's histogram (zeroed behind it for the next level)
+__global__ __launch_bounds__(256) void topk_grid_select_kernel(const TopkControl *__restrict__ ctl, TopkSlot *__restrict__ slots, uint32_t *__restrict__ hist,
+                                                               uint32_t slot_cap, int level) {
+    __shared__ uint32_t s_hist[kTopkBins];
+    __shared__ uint32_t s_wtot[4], s_res[3];
+    const uint32_t ns = grid_slots(ctl, slot_cap);
+    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x) {
+        TopkSel sel = slots[s].sel;
+        if (!slots[s].valid || sel.done) continue;
+        uint32_t *h = hist + static_cast<size_t>(s) * kTopkBins;
+        for (uint32_t c = threadIdx.x; c < kTopkBins; c += 256u) {
+            s_hist[c] = h[c];
+            h[c] = 0u;
+        }
+        __syncthreads();
+        select_digit<256>(s_hist, sel.need, s_wtot, s_res);
+        sel_apply(sel, level, s_res[0], s_res[1], s_res[2]);
+        if (threadIdx.x == 0u) slots[s].sel = sel;
+        __syncthreads();
+    }
+}
+
+// one workgroup per slot: the tiles' counts become their bases (exclusive scan in tile order); the slots past m get the filler
+__global__ __launch_bounds__(1024) void topk_grid_scan_kernel(TopkArgs a, const TopkControl *__restrict__ ctl, const TopkSlot *__restrict__ slots,
+                                                              uint2 *__restrict__ tilecnt, uint32_t slot_cap) {
+    __shared__ uint32_t s_wtot[2 * 16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t ns = grid_slots(ctl, slot_cap);
+    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x) {
+        const TopkSlot sl = slots[s];
+        if (!sl.valid) continue;
+        fill_tail(a.out_keys + static_cast<size_t>(sl.seg) * a.k, a.out_indices ? a.out_indices + static_cast<size_t>(sl.seg) * a.k : nullptr, sl.m,
+                  a.k, 1024u);
+        uint32_t carry_a = 0, carry_b = 0;
+        for (uint32_t t0 = 0; t0 < sl.tiles; t0 += 1024u) {
+            const uint32_t t = t0 + tid;
+            const uint2 v = t < sl.tiles ? tilecnt[sl.tile_base + t] : make_uint2(0u, 0u);
+            uint32_t ia = v.x, ib = v.y;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t ta = __shfl_up(ia, o), tb = __shfl_up(ib, o);
+                if (lane >= static_cast<uint32_t>(o)) {
+                    ia += ta;
+                    ib += tb;
+                }
+            }
+            if (lane == 63u) {
+                s_wtot[wave] = ia;
+                s_wtot[16 + wave] = ib;
+            }
+            __syncthreads();
+            uint32_t add_a = carry_a, add_b = carry_b, all_a = carry_a, all_b = carry_b;
+            for (uint32_t w = 0; w < 16u; ++w) {
+                if (w < wave) {
+                    add_a += s_wtot[w];
+                    add_b += s_wtot[16 + w];
+                }
+                all_a += s_wtot[w];
+                all_b += s_wtot[16 + w];
+            }
+            if (t < sl.tiles) tilecnt[sl.tile_base + t] = make_uint2(add_a + ia - v.x, add_b + ib - v.y);
+            carry_a = all_a;
+            carry_b = all_b;
+            __syncthreads();
+        }
+    }
+}
+
+// VRS_TOPK_SORTED, k <= THREADS * ITEMS: one workgroup per segment sorts its m survivors by r, stably, over the bits that vary
+template <int THREADS, int ITEMS>
+__global__ __launch_bounds__(THREADS) void topk_sort_small_kernel(TopkArgs a) {
+    constexpr int WAVES = THREADS / 64, CAP = THREADS * ITEMS;
+    __shared__ uint32_t s_keys[CAP];
+    __shared__ uint32_t s_vals[CAP];
+    __shared__ uint32_t s_hist[WAVES * 256];
+    __shared__ uint32_t s_tmp[WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t seg0 = wave * (ITEMS * 64) + lane;
+    const bool largest = (a.flags & kTopkLargest) != 0;
+    for (uint32_t seg = blockIdx.x; seg < a.num_segments; seg += gridDim.x) {
+        uint32_t b, e;
+        (void)topk_tier(a.offsets[seg], a.offsets[seg + 1u], a.n, 0u, &b, &e);
+        const uint32_t m = min(a.k, e - b);
+        if (m < 2u || m > static_cast<uint32_t>(CAP)) continue;
+        uint32_t *ok = a.out_keys + static_cast<size_t>(seg) * a.k;
+        uint32_t *oi = a.out_indices ? a.out_indices + static_cast<size_t>(seg) * a.k : nullptr;
+        uint32_t key[ITEMS], val[ITEMS];
+        const uint32_t k0 = topk_rank(ok[0], a.key_type, largest);
+        uint32_t diff = 0;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            const uint32_t idx = seg0 + i * 64;
+            key[i] = idx < m ? topk_rank(ok[idx], a.key_type, largest) : k0;
+            val[i] = (idx < m && oi) ? oi[idx] : 0u;
+            diff |= key[i] ^ k0;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) diff |= __shfl_xor(diff, o);
+        if constexpr (WAVES > 1) {
+            if (lane == 0u) s_tmp[wave] = diff;
+            __syncthreads();
+#pragma unroll
+            for (int v = 0; v < WAVES; ++v) diff |= s_tmp[v];
+            __syncthreads();
+        }
+        if (diff == 0u) continue;  // every survivor equal: already in index order
+        const uint32_t width = 32u - static_cast<uint32_t>(__clz(diff));
+        for (uint32_t shift = 0; shift < width; shift += 8u) local_pass<THREADS, ITEMS, 8, true, true>(key, val, s_keys, s_vals, s_hist, s_tmp, shift, m);
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            const uint32_t idx = seg0 + i * 64;
+            if (idx < m) {
+                ok[idx] = topk_unrank(key[i], a.key_type, largest);
+                if (oi) oi[idx] = val[i];
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t segment_m(const TopkArgs &a, uint32_t seg) {
+    uint32_t b, e;
+    (void)topk_tier(a.offsets[seg], a.offsets[seg + 1u], a.n, 0u, &b, &e);
+    return min(a.k, e - b);
+}
+
+__global__ __launch_bounds__(256) void topk_sort_prep_kernel(TopkArgs a, uint32_t *__restrict__ sk, uint32_t *__restrict__ sv) {
+    const uint32_t total = a.num_segments * a.k;
+    const bool largest = (a.flags & kTopkLargest) != 0;
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < total; s += gridDim.x * 256u) {
+        const uint32_t seg = s / a.k, j = s - seg * a.k;
+        const bool in = j < segment_m(a, seg);
+        sk[s] = in ? topk_rank(a.out_keys[s], a.key_type, largest) : 0xFFFFFFFFu;
+        sv[s] = in && a.out_indices ? a.out_indices[s] : 0xFFFFFFFFu;
+    }
+}
+
+__global__ __launch_bounds__(256) void topk_sort_offsets_kernel(TopkArgs a) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= a.num_segments; i += gridDim.x * 256u) a.out_keys[i] = i * a.k;
+}
+
+__global__ __launch_bounds__(256) void topk_sort_back_kernel(TopkArgs a, const uint32_t *__restrict__ sk, const uint32_t *__restrict__ sv) {
+    const uint32_t total = a.num_segments * a.k;
+    const bool largest = (a.flags & kTopkLargest) != 0;
+    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < total; s += gridDim.x * 256u) {
+        const uint32_t seg = s / a.k, j = s - seg * a.k;
+        const bool in = j < segment_m(a, seg);
+        a.out_keys[s] = in ? topk_unrank(sk[s], a.key_type, largest) : 0xFFFFFFFFu;
+        if (a.out_indices) a.out_indices[s] = in ? sv[s] : 0xFFFFFFFFu;
+    }
+}
+
+uint32_t grid_of(uint64_t work, uint32_t cap) { return static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>(work, cap))); }
+
+}  // namespace
+
+hipError_t launch_topk(hipStream_t stream, const TopkArgs &a, const TopkLayout &L) {
+    auto *ctl = reinterpret_cast<TopkControl *>(a.scratch + L.control);
+    auto *list = reinterpret_cast<uint32_t *>(a.scratch + L.list);
+    auto *slots = reinterpret_cast<TopkSlot *>(a.scratch + L.slots);
+    auto *hist = reinterpret_cast<uint32_t *>(a.scratch + L.hist);
+    auto *tilecnt = reinterpret_cast<uint2 *>(a.scratch + L.tiles);
+    hipError_t e = hipMemsetAsync(ctl, 0, sizeof(TopkControl), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t S = a.num_segments;
+    hipLaunchKernelGGL(topk_classify_kernel, dim3(grid_of((static_cast<uint64_t>(S) + 255u) / 256u, 0xFFFFFFFFu)), dim3(256), 0, stream, a, ctl, list,
+                       slots, L.slot_cap, L.tile_cap);
+    hipLaunchKernelGGL((topk_workgroup_kernel<256, 32, true>), dim3(grid_of(S, 8192u)), dim3(256), 0, stream, a, ctl, list);
+    if (a.n > kTopkLdsCap)  // (else no segment is longer than the LDS tier's cap)
+        hipLaunchKernelGGL((topk_workgroup_kernel<1024, 16, false>), dim3(grid_of(S, 1024u)), dim3(1024), 0, stream, a, ctl, list);
+    if (L.slot_cap != 0u && a.grid_min_keys != 0u && a.n >= a.grid_min_keys) {
+        const uint32_t walkers = grid_of(L.tile_cap, 1024u), per_slot = grid_of(L.slot_cap, 1024u);
+        hipLaunchKernelGGL(topk_grid_init_kernel, dim3(per_slot), dim3(256), 0, stream, ctl, hist, L.slot_cap);
+        for (int level = 0; level < kTopkLevels; ++level) {
+            hipLaunchKernelGGL(topk_grid_walk_kernel<0>, dim3(walkers), dim3(kGridThreads), 0, stream, a, ctl, slots, hist, tilecnt, L.slot_cap,
+                               L.tile_cap, level);
+            hipLaunchKernelGGL(topk_grid_select_kernel, dim3(per_slot), dim3(256), 0, stream, ctl, slots, hist, L.slot_cap, level);
+        }
+        hipLaunchKernelGGL(topk_grid_walk_kernel<1>, dim3(walkers), dim3(kGridThreads), 0, stream, a, ctl, slots, hist, tilecnt, L.slot_cap, L.tile_cap, 0);
+        hipLaunchKernelGGL(topk_grid_scan_kernel, dim3(per_slot), dim3(1024), 0, stream, a, ctl, slots, tilecnt, L.slot_cap);
+        hipLaunchKernelGGL(topk_grid_walk_kernel<2>, dim3(walkers), dim3(kGridThreads), 0, stream, a, ctl, slots, hist, tilecnt, L.slot_cap, L.tile_cap, 0);
+    }
+    if ((a.flags & kTopkSorted) != 0 && !L.big_sort) {
+        if (a.k <= 256u)
+            hipLaunchKernelGGL((topk_sort_small_kernel<64, 4>), dim3(grid_of(S, 16384u)), dim3(64), 0, stream, a);
+        else
+            hipLaunchKernelGGL((topk_sort_small_kernel<256, 16>), dim3(grid_of(S, 8192u)), dim3(256), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_sort_prep(hipStream_t stream, const TopkArgs &a, const TopkLayout &L) {
+    auto *area = reinterpret_cast<uint32_t *>(a.scratch + L.sort);
+    const size_t sk = static_cast<size_t>(a.num_segments) * a.k;
+    const uint32_t blocks = grid_of((sk + 255u) / 256u, 8192u);
+    hipLaunchKernelGGL(topk_sort_prep_kernel, dim3(blocks), dim3(256), 0, stream, a, area, area + 2u * sk);
+    hipLaunchKernelGGL(topk_sort_offsets_kernel, dim3(grid_of((a.num_segments + 256u) / 256u, 8192u)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_sort_back(hipStream_t stream, const TopkArgs &a, const TopkLayout &L) {
+    auto *area = reinterpret_cast<uint32_t *>(a.scratch + L.sort);
+    const size_t sk = static_cast<size_t>(a.num_segments) * a.k;
+    hipLaunchKernelGGL(topk_sort_back_kernel, dim3(grid_of((sk + 255u) / 256u, 8192u)), dim3(256), 0, stream, a, area, area + 2u * sk);
+    return hipGetLastError();
+}
+
+static_assert(64 * 4 >= 256 && 256 * 16 >= static_cast<int>(kTopkSortCap), "the sort kernels hold every k they are launched for");
+
+}  // namespace vrs

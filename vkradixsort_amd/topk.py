@@ -1,0 +1,97 @@
+"""Top-k selection: the k smallest or largest keys of every segment and their positions by radix select (vrs_topk_segments).
+
+topk_segments works on Buffers of a GPUContext; topk is torch.topk(x, k, dim=-1) of a 1-D or 2-D int32 / float32 tensor, on torch's
+current stream.
+"""
+from __future__ import annotations
+
+import ctypes
+
+from . import capi, engine
+from .capi import VrsError
+from .segmented import _context_for
+
+_KEY_TYPES = {"u32": capi.VRS_TOPK_U32, "i32": capi.VRS_TOPK_I32, "f32": capi.VRS_TOPK_F32}
+
+
+def scratch_bytes(num_elements: int, num_segments: int, k: int, largest: bool = False, sorted: bool = True) -> int:
+    """Bytes of scratch vrs_topk_segments needs for this shape (no device)."""
+    out = ctypes.c_uint64()
+    lib = capi.load_library()
+    flags = (capi.VRS_TOPK_LARGEST if largest else 0) | (capi.VRS_TOPK_SORTED if sorted else 0)
+    rc = lib.vrs_topk_scratch_bytes(num_elements, num_segments, k, flags, ctypes.byref(out))
+    if rc != capi.VRS_OK:
+        raise VrsError(rc, lib.vrs_last_error(None).decode())
+    return out.value
+
+
+def topk_segments(ctx, keys, offsets, num_elements: int, num_segments: int, k: int, out_keys, out_indices=None, scratch=None,
+                  key_type: str = "u32", largest: bool = False, sorted: bool = True) -> None:
+    """For every segment i = keys[offsets[i], offsets[i+1]) the min(k, length) smallest (largest=True: largest) keys, ties lowest index
+    first, into out_keys[i*k ...] and their positions within the segment into out_indices[i*k ...]; slots past the segment's length get
+    0xFFFFFFFF.  sorted=True: in that order, else in some order.  key_type "u32", "i32" or "f32" fixes how the bit patterns compare.
+    scratch: a Buffer of at least scratch_bytes(...) bytes.  Stream-ordered on the context's stream."""
+    if key_type not in _KEY_TYPES:
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, f"key_type must be one of {sorted(_KEY_TYPES)}")
+    if scratch is None:
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, "topk_segments needs a scratch Buffer of scratch_bytes(...) bytes")
+    flags = (capi.VRS_TOPK_LARGEST if largest else 0) | (capi.VRS_TOPK_SORTED if sorted else 0)
+    ctx.check(ctx.lib.vrs_topk_segments(ctx.handle, keys.handle, num_elements, offsets.handle, num_segments, k, _KEY_TYPES[key_type], flags,
+                                        out_keys.handle, out_indices.handle if out_indices is not None else None, scratch.handle))
+
+
+def topk_stats(ctx) -> dict:
+    """Segments the context's top-k calls gave each tier so far (cumulative)."""
+    c = [ctypes.c_uint64() for _ in range(3)]
+    ctx.check(ctx.lib.vrs_topk_stats(ctx.handle, *(ctypes.byref(v) for v in c)))
+    return {"lds": c[0].value, "block": c[1].value, "grid": c[2].value}
+
+
+def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
+    """torch.topk(x, k, dim=-1, largest, sorted) of a contiguous 1-D or 2-D int32 or float32 tensor on a GPU: one call for all rows.
+
+    Returns (values, indices), indices int64 positions within the row.  Ties are broken by the lower index, so the result is that of
+    a stable sort of each row, sliced; torch.topk equals it on rows without ties.  Floats compare by the IEEE-754 total order:
+    -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN (a NaN with its sign bit set is the smallest key, one without it the largest;
+    -0.0 is below +0.0), where torch treats every NaN as the largest value and -0.0 equal to +0.0."""
+    import torch
+
+    if not x.is_cuda:
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, "topk takes a tensor on a GPU")
+    if x.dim() not in (1, 2) or not x.is_contiguous():
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, "topk takes a contiguous 1-D or 2-D tensor")
+    if dim not in (-1, x.dim() - 1):
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, "topk selects along the last dimension only")
+    if x.dtype == torch.int32:
+        key_type = capi.VRS_TOPK_I32
+    elif x.dtype == torch.float32:
+        key_type = capi.VRS_TOPK_F32
+    else:
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, f"topk takes int32 or float32, not {x.dtype}")
+    rows, length = (1, x.shape[0]) if x.dim() == 1 else tuple(x.shape)
+    if k < 0 or k > length:
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, f"k = {k} is outside [0, {length}]")
+    n = rows * length
+    if n >= 1 << 32 or rows * k >= 1 << 32:
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, "topk takes fewer than 2^32 elements")
+    shape = (k,) if x.dim() == 1 else (rows, k)
+    device = x.device
+    values = torch.empty(shape, dtype=x.dtype, device=device)
+    idx = torch.empty(shape, dtype=torch.int32, device=device)
+    if k == 0 or rows == 0:
+        return values, idx.long()
+    ctx = _context_for(torch, device)
+    bounds = torch.arange(rows + 1, dtype=torch.int64, device=device) * length
+    offsets = ((bounds + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)  # uint32 bit patterns
+    flags = (capi.VRS_TOPK_LARGEST if largest else 0) | (capi.VRS_TOPK_SORTED if sorted else 0)
+    scratch = torch.empty(max(scratch_bytes(n, rows, k, largest, sorted), 4), dtype=torch.uint8, device=device)
+    S = engine.Buffer.BufferSettings
+    tensors = [x, offsets, values, idx, scratch]
+    bufs = [engine.Buffer(ctx, S(max(t.numel() * t.element_size(), 4)), device_ptr=t.data_ptr()) for t in tensors]
+    try:
+        ctx.check(ctx.lib.vrs_topk_segments(ctx.handle, bufs[0].handle, n, bufs[1].handle, rows, k, key_type, flags, bufs[2].handle,
+                                            bufs[3].handle, bufs[4].handle))
+    finally:
+        for b in bufs:
+            b.release()
+    return values, idx.long()

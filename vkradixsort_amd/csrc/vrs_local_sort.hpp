@@ -28,6 +28,23 @@ __device__ __forceinline__ void store_sorted(uint4 *p, const uint4 &q) {
     }
 }
 
+// k[4 j + c] = slot 4 (j STRIDE + t) + c of src, for the slots [0, words): a bucket as rows of 16-byte vectors, the way both bodies below
+// take it.  t: the thread's index in its row -- threadIdx.x for a workgroup, threadIdx.x & 63 for a wave.
+template <int STRIDE, int VEC>
+__device__ __forceinline__ void load_rows(uint32_t (&k)[4 * VEC], const uint32_t *src, uint32_t words, uint32_t t) {
+    const uint32_t nvec = (words + 3u) / 4u;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        uint32_t v = j * STRIDE + t;
+        if (j == VEC - 1) v = v < nvec ? v : nvec - 1u;  // only the last row can reach behind the bucket
+        const uint4 q = reinterpret_cast<const uint4 *>(src)[v];
+        k[4 * j] = q.x;
+        k[4 * j + 1] = q.y;
+        k[4 * j + 2] = q.z;
+        k[4 * j + 3] = q.w;
+    }
+}
+
 // ALIGNED_IN: mis_in == 0 (a bucket read from its own 16-byte aligned region, written elsewhere): the slots without a key are then
 // the LAST ones -- which reach up to three slots into the row before the last when the output's misalignment adds a row.
 template <int THREADS, int VEC, bool GUARD, bool STREAM = false, bool ALIGNED_IN = false>
@@ -245,9 +262,9 @@ __device__ __forceinline__ void wave_scan512(uint32_t *tbl, uint32_t lane, uint3
     reinterpret_cast<uint4 *>(tbl)[2 * lane + 1] = ob;
 }
 // One WAVE sorts a bucket of up to 64 * 28 slots (no workgroup barrier: the LDS executes one wave's operations in order): the same two
-// 9-bit passes, slots and dummy counters as lean_sort_body, one 512-counter table reused by both passes.  mis_in / ALIGNED_IN / STREAM:
+// 9-bit passes, slots and dummy counters as lean_sort_body, one 512-counter table reused by both passes.  mis_in / STREAM / ALIGNED_IN:
 // see lean_sort_body.
-template <int VEC, bool GUARD, bool ALIGNED_IN = false, bool STREAM = false>
+template <int VEC, bool GUARD, bool STREAM = false, bool ALIGNED_IN = false>
 __device__ __forceinline__ void wave_sort_body(uint32_t (&k)[4 * VEC], uint32_t *abase, uint32_t mis, uint32_t n, uint32_t *s_keys,
                                                uint32_t *tbl, bool guard1, bool guard2, uint32_t mis_in) {
     constexpr int ITEMS = 4 * VEC;
@@ -571,12 +588,6 @@ __device__ __forceinline__ void local_sort_packed_pairs_to(const uint32_t *src, 
             else bucket_vals[idx] = val[i];
         }
     }
-}
-
-template <int THREADS, int ITEMS, bool PAIRS>
-__device__ __forceinline__ void local_sort_bucket(uint32_t *bucket, uint32_t *bucket_vals, uint32_t n, uint32_t *s_keys,
-                                                  uint32_t *s_vals, uint32_t *s_hist, uint32_t *s_tmp) {
-    local_sort_bucket_to<THREADS, ITEMS, PAIRS>(bucket, bucket_vals, bucket, bucket_vals, n, s_keys, s_vals, s_hist, s_tmp);
 }
 
 // The local sort is the last kernel of a hybrid sort and LDS-bound: it has HBM time to spare, so it also clears the look-back

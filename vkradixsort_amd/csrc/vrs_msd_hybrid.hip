@@ -371,7 +371,7 @@ __device__ __forceinline__ void rearm_reservation(uint32_t *__restrict__ cursors
         for (uint32_t c = threadIdx.x; c < 256u; c += threads) cursors[b * 256u + c] = 0;
 }
 
-// (local_pass, local_sort_bucket: vrs_local_sort.hpp -- the pool form's pairs use them too)
+// (local_pass, local_sort_bucket_to: vrs_local_sort.hpp -- the pool form's pairs use them too)
 // ---- the local sort of bare uint32 keys (round 3 form).  One workgroup per bucket of the MSD partition, the bucket sorted by its
 // low 18 bits inside LDS in two 9-bit passes and written back in place -- the algorithm of local_pass above (returning LDS
 // atomics rank the keys; pass 1 over bare keys in any order of ties with ONE counter table, pass 2 stable with one table per
@@ -609,13 +609,13 @@ __global__ __launch_bounds__(THREADS, 4) void msd_local_sort_pairs_kernel(uint32
     if (n == 0 || n > CAP) return;
     uint32_t *bucket = keys + begin, *bvals = values + begin;
     const uint32_t used = (n + THREADS - 1u) / THREADS;
-    if (used <= 2) local_sort_bucket<THREADS, 2, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
-    else if (used <= 4) local_sort_bucket<THREADS, 4, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
-    else if (used <= 6) local_sort_bucket<THREADS, 6, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
-    else if (used <= 8) local_sort_bucket<THREADS, 8, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
-    else if (used <= 10) local_sort_bucket<THREADS, 10, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
-    else if (used <= 12) local_sort_bucket<THREADS, 12, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
-    else local_sort_bucket<THREADS, kLocalPairItems, true>(bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    if (used <= 2) local_sort_bucket_to<THREADS, 2, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    else if (used <= 4) local_sort_bucket_to<THREADS, 4, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    else if (used <= 6) local_sort_bucket_to<THREADS, 6, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    else if (used <= 8) local_sort_bucket_to<THREADS, 8, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    else if (used <= 10) local_sort_bucket_to<THREADS, 10, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    else if (used <= 12) local_sort_bucket_to<THREADS, 12, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
+    else local_sort_bucket_to<THREADS, kLocalPairItems, true>(bucket, bvals, bucket, bvals, n, s_keys, s_vals, s_hist, s_tmp);
 }
 
 // 64-bit keys: the bucket's keys differ only in their low `shift` bits (up to 50): ceil(shift / 9) LDS passes, the first in any

@@ -16,26 +16,11 @@ namespace {
 // read like lean_sort_bucket (vrs_msd_hybrid.hip) reads a bucket of the counted form, sorted by lean_sort_body, written -- unlike
 // there -- somewhere else: to the bucket's final place in the caller's buffer, whose misalignment is the OUTPUT's alone.
 template <int THREADS, int VEC>
-__device__ __forceinline__ void slack_load(uint32_t (&k)[4 * VEC], const uint32_t *src, uint32_t n) {
-    const uint32_t nvec = (n + 3u) / 4u;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        uint32_t v = j * THREADS + threadIdx.x;
-        if (j == VEC - 1) v = v < nvec ? v : nvec - 1u;  // only the last row can reach behind the bucket
-        const uint4 t = reinterpret_cast<const uint4 *>(src)[v];
-        k[4 * j] = t.x;
-        k[4 * j + 1] = t.y;
-        k[4 * j + 2] = t.z;
-        k[4 * j + 3] = t.w;
-    }
-}
-
-template <int THREADS, int VEC>
 __device__ __attribute__((noinline)) void slack_sort_guarded(const uint32_t *src, uint32_t *abase, uint32_t mis, uint32_t n, uint32_t *s_keys,
                                                             uint32_t *s_hist2, uint32_t *s_tmp, uint32_t guards) {
     // (out of line, loading the bucket again: this copy's registers must not cost the common path its occupancy -- lean_sort_bucket)
     uint32_t k[4 * VEC];
-    slack_load<THREADS, VEC>(k, src, n);
+    load_rows<THREADS, VEC>(k, src, n, threadIdx.x);
     lean_sort_body<THREADS, VEC, true, true, true>(k, abase, mis, n, s_keys, s_hist2, s_tmp, (guards & 1u) != 0u, (guards & 2u) != 0u, 0u);
 }
 
@@ -45,7 +30,7 @@ __device__ __forceinline__ void slack_sort_bucket(const uint32_t *src, uint32_t 
     constexpr int WAVES = THREADS / 64;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint32_t k[4 * VEC];
-    slack_load<THREADS, VEC>(k, src, n);
+    load_rows<THREADS, VEC>(k, src, n, threadIdx.x);
     {   // every counter table zeroed here (lean_sort_bucket does the same): WAVES tables of pass 2, then pass 1's
         constexpr uint32_t kVecs = (WAVES + 1) * kLeanRow / 4;
         for (uint32_t c = tid; c < kVecs; c += THREADS) reinterpret_cast<uint4 *>(s_hist2)[c] = make_uint4(0, 0, 0, 0);
@@ -216,31 +201,17 @@ __global__ __launch_bounds__(THREADS, (PACKED && THREADS == 512) ? 6 : 4) void p
 // (msd_local_sort_wave_kernel's idea, vrs_msd_hybrid.hip: 16 independent buckets per CU instead of workgroups whose fixed work is most of
 // their life) -- with it the pool form is worth taking from about 10^7 keys on.
 template <int VEC>
-__device__ __forceinline__ void slack_wave_load(uint32_t (&k)[4 * VEC], const uint32_t *src, uint32_t n) {
-    const uint32_t lane = threadIdx.x & 63u, nvec = (n + 3u) / 4u;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        uint32_t v = j * 64 + lane;
-        if (j == VEC - 1) v = v < nvec ? v : nvec - 1u;
-        const uint4 t = reinterpret_cast<const uint4 *>(src)[v];
-        k[4 * j] = t.x;
-        k[4 * j + 1] = t.y;
-        k[4 * j + 2] = t.z;
-        k[4 * j + 3] = t.w;
-    }
-}
-template <int VEC>
 __device__ __attribute__((noinline)) void slack_wave_sort_guarded(const uint32_t *src, uint32_t *abase, uint32_t mis, uint32_t n, uint32_t *s_keys, uint32_t *tbl,
                                                                  uint32_t skew) {
     uint32_t k[4 * VEC];
-    slack_wave_load<VEC>(k, src, n);
+    load_rows<64, VEC>(k, src, n, threadIdx.x & 63u);
     wave_sort_body<VEC, true, true, true>(k, abase, mis, n, s_keys, tbl, (skew & 1u) != 0u, (skew & 2u) != 0u, 0u);
 }
 template <int VEC>
 __device__ __forceinline__ void slack_wave_sort_bucket(const uint32_t *src, uint32_t *abase, uint32_t mis, uint32_t n, uint32_t *s_keys, uint32_t *tbl) {
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t k[4 * VEC];
-    slack_wave_load<VEC>(k, src, n);
+    load_rows<64, VEC>(k, src, n, threadIdx.x & 63u);
     // the table zeroed: 576 words, two 16-byte stores per lane + one more from the first 16 lanes
     reinterpret_cast<uint4 *>(tbl)[2 * lane] = make_uint4(0, 0, 0, 0);
     reinterpret_cast<uint4 *>(tbl)[2 * lane + 1] = make_uint4(0, 0, 0, 0);
@@ -267,24 +238,15 @@ __global__ __launch_bounds__(64, 4) void pool_local_sort_wave_kernel(const uint3
     const uint32_t *src;
     uint32_t *abase, mis, n;
     if (!pool_bucket<64, 64u * 4u * MAXVEC, SUBBITS>(slack, keys_out, msd, pool, cursors, dev_head, host_head, stamp, host_log, retry, par, src, abase, mis, n)) return;
-    const uint32_t rows = (mis + n + 255u) / 256u;
-    if constexpr (MAXVEC == 4) {
-        switch (rows) {
-            case 1: slack_wave_sort_bucket<1>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 2: slack_wave_sort_bucket<2>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 3: slack_wave_sort_bucket<3>(src, abase, mis, n, s_keys, s_tbl); break;
-            default: slack_wave_sort_bucket<4>(src, abase, mis, n, s_keys, s_tbl); break;
-        }
-    } else {
-        switch (rows) {
-            case 1: slack_wave_sort_bucket<1>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 2: slack_wave_sort_bucket<2>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 3: slack_wave_sort_bucket<3>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 4: slack_wave_sort_bucket<4>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 5: slack_wave_sort_bucket<5>(src, abase, mis, n, s_keys, s_tbl); break;
-            case 6: slack_wave_sort_bucket<6>(src, abase, mis, n, s_keys, s_tbl); break;
-            default: slack_wave_sort_bucket<7>(src, abase, mis, n, s_keys, s_tbl); break;
-        }
+    static_assert(MAXVEC == 7, "one row count per case");
+    switch ((mis + n + 255u) / 256u) {
+        case 1: slack_wave_sort_bucket<1>(src, abase, mis, n, s_keys, s_tbl); break;
+        case 2: slack_wave_sort_bucket<2>(src, abase, mis, n, s_keys, s_tbl); break;
+        case 3: slack_wave_sort_bucket<3>(src, abase, mis, n, s_keys, s_tbl); break;
+        case 4: slack_wave_sort_bucket<4>(src, abase, mis, n, s_keys, s_tbl); break;
+        case 5: slack_wave_sort_bucket<5>(src, abase, mis, n, s_keys, s_tbl); break;
+        case 6: slack_wave_sort_bucket<6>(src, abase, mis, n, s_keys, s_tbl); break;
+        default: slack_wave_sort_bucket<7>(src, abase, mis, n, s_keys, s_tbl); break;
     }
 }
 

@@ -369,6 +369,59 @@ int vrs_topk_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, uint3
 int vrs_topk_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments);
 
 /*
+ * Run-length encoding (build extension; no reference counterpart -- the reference's callers find each cell's or tile's [start, end)
+ * in the sorted ids themselves): n keys of key_bytes (4 or 8) each, in any order, as maximal runs of bit-identical consecutive keys
+ * (torch.unique_consecutive).  With R runs: out_keys[j] = the key of run j, out_offsets[j] = its first position and out_offsets[R] = n,
+ * out_counts[j] = its length, out_run_ids[i] = the run of element i, and out_num_runs[0] = R, written on the device.  Every output but
+ * out_num_runs may be NULL.  `keys` is never written; output entries past R (past R + 1 for out_offsets) are never written, nor are the
+ * bytes of an output buffer beyond n (n + 1) entries.  n == 0: out_num_runs[0] = 0 and nothing else.
+ * One pass over the keys: tiles of 4096 keys taken in order from a ticket, a head flag per key (i == 0 or k[i] != k[i-1]), ranks by
+ * __ballot / mbcnt, the runs in front of a tile by decoupled look-back; the counts from the offsets by a second, short launch.
+ * scratch: at least vrs_run_length_encode_scratch_bytes(n, key_bytes, flags) bytes, with VRS_RLE_COUNTS in flags whenever out_counts
+ * is given and out_offsets is NULL (the offsets then live in the scratch): at most (VRS_RLE_COUNTS ? 4 n : 0) + n / 256 + 1024 bytes.
+ * Contents on entry unspecified, afterwards unspecified.  NULL ctx, keys, out_num_runs or scratch, a key_bytes other than 4 or 8 and
+ * undersized buffers (n entries; n + 1 for out_offsets): VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Stream-ordered on the
+ * context's stream; the call only enqueues (after settling a pending one-call sort).
+ */
+enum { VRS_RLE_COUNTS = 1 }; /* scratch flag */
+int vrs_run_length_encode(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, int key_bytes, vrs_buffer out_keys,
+                          vrs_buffer out_offsets, vrs_buffer out_counts, vrs_buffer out_run_ids, vrs_buffer out_num_runs,
+                          vrs_buffer scratch);
+/* the scratch vrs_run_length_encode needs: a pure function, needs no device (0 for n == 0) */
+int vrs_run_length_encode_scratch_bytes(uint32_t num_elements, int key_bytes, int flags, uint64_t *bytes);
+
+/*
+ * Unique (build extension; no reference counterpart): the distinct keys of n keys in ascending order, how often each occurs and which of
+ * them each element is (torch.unique(x, sorted=True, return_inverse=True, return_counts=True)).  key_type (vrs_unique_key_type) fixes
+ * the width and the order: the rank r(x) = x (U32, U64), x ^ 2^31 (I32), x ^ 2^63 (I64), the VRS_KEYS_FLOAT32_TO_SORTABLE map (F32)
+ * and the same map widened (F64): IEEE-754 total order, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.  Equality is equality of bit
+ * patterns: -0.0 and +0.0 are two keys and NaNs of the same bits are one -- where torch.unique merges -0.0 into +0.0 and keeps every NaN
+ * apart.  out_keys[j] = the j-th smallest distinct key (its bit pattern), out_counts[j] = its occurrences, out_inverse[i] = the j of
+ * element i, out_num_runs[0] = R, written on the device.  out_counts and out_inverse may be NULL.  The same guarantees as
+ * vrs_run_length_encode for `keys`, entries past R and bytes past n entries; n == 0: out_num_runs[0] = 0 and nothing else.
+ * Pipeline: one kernel writes r(keys) (and, for the inverse, the positions 0 .. n-1 beside them) into the scratch, the stable one-call
+ * sort sorts them there (vrs_sort_pairs_u32 / vrs_sort_pairs_u64 with the inverse, vrs_sort_keys_u32 / vrs_sort_keys_u64 without), and
+ * the run-length encode runs over the sorted ranks, undoing r as it writes out_keys and scattering run ids through the sorted positions.
+ * scratch: at least vrs_unique_scratch_bytes(n, key_type, flags) bytes with VRS_UNIQUE_INVERSE / VRS_UNIQUE_COUNTS set for the outputs
+ * given: at most (2 * key bytes + (VRS_UNIQUE_INVERSE ? 8 : 0) + (VRS_UNIQUE_COUNTS ? 4 : 0)) * n + n / 256 + 2048 bytes.  Contents on
+ * entry unspecified, afterwards unspecified.  NULL ctx, keys, out_keys, out_num_runs or scratch, an unknown key_type and undersized
+ * buffers: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
+ * Blocking, as the segmented sorts': after settling a pending one-call sort the call may wait for the inner sort's plan head (bounded by
+ * VRS_TUNE_PLAN_WAIT_MS -> VRS_ERROR_TIMEOUT, the encode then not enqueued), never for the sort itself; the inner sort counts in the
+ * one-call statistics.
+ */
+typedef enum vrs_unique_key_type {
+    VRS_UNIQUE_U32 = 0, VRS_UNIQUE_I32 = 1, VRS_UNIQUE_F32 = 2,
+    VRS_UNIQUE_U64 = 3, VRS_UNIQUE_I64 = 4, VRS_UNIQUE_F64 = 5
+} vrs_unique_key_type;
+enum { VRS_UNIQUE_INVERSE = 1, VRS_UNIQUE_COUNTS = 2 }; /* scratch flags */
+int vrs_unique(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, int key_type, vrs_buffer out_keys,
+               vrs_buffer out_counts /* may be NULL */, vrs_buffer out_inverse /* may be NULL */, vrs_buffer out_num_runs,
+               vrs_buffer scratch);
+/* the scratch vrs_unique needs: a pure function, needs no device (0 for n == 0) */
+int vrs_unique_scratch_bytes(uint32_t num_elements, int key_type, int flags, uint64_t *bytes);
+
+/*
  * Key preprocessing the reference leaves to the integrator ("you have to preprocess negative numbers",
  * README.md:154-155): in-place, order-preserving maps between int32 / float32 bit patterns and the uint32
  * keys the sort orders.  Asynchronous.  Apply *_TO_SORTABLE before the four passes and the inverse after.

@@ -85,6 +85,11 @@ VRS_TOPK_LARGEST, VRS_TOPK_SORTED = 1, 2
 VRS_TOPK_LDS, VRS_TOPK_BLOCK, VRS_TOPK_GRID = 0, 1, 2
 TOPK_LDS_MAX = 8192
 TOPK_SORT_IN_LDS_MAX_K = 4096  # VRS_TOPK_SORTED beyond this k sorts the survivors with vrs_sort_segments_pairs_u32
+# run-length encoding and unique: scratch flags, key types, and the encode's tile (keys per look-back status word)
+VRS_RLE_COUNTS = 1
+VRS_UNIQUE_U32, VRS_UNIQUE_I32, VRS_UNIQUE_F32, VRS_UNIQUE_U64, VRS_UNIQUE_I64, VRS_UNIQUE_F64 = 0, 1, 2, 3, 4, 5
+VRS_UNIQUE_INVERSE, VRS_UNIQUE_COUNTS = 1, 2
+RLE_TILE = 4096
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -216,6 +221,10 @@ _SIGNATURES = [
     ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
     ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
     ("vrs_topk_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
+    ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vrs_unique_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]

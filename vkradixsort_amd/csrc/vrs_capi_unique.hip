@@ -1,0 +1,124 @@
+// vrs_capi_unique.hip -- the C ABI of run-length encoding (vrs_run_length_encode) and unique (vrs_unique): argument checks, the scratch
+// layouts, the launches of vrs_unique.hip, and for unique the stable one-call sort of the mapped keys on views of the scratch.
+#include "vrs_host.hpp"
+#include "vrs_unique.hpp"
+
+using namespace vrsh;
+
+namespace {
+
+constexpr int kKnownRleFlags = vrs::kRleCounts;
+constexpr int kKnownUniqueFlags = vrs::kUniqueInverse | vrs::kUniqueCounts;
+
+bool known_key_type(int key_type) { return key_type >= vrs::kUniqueU32 && key_type <= vrs::kUniqueF64; }
+
+// n == 0: R = 0 is the whole result
+int write_no_runs(vrs_context ctx, vrs_buffer out_num_runs) {
+    VRS_HIP(ctx, hipMemsetAsync(out_num_runs->ptr, 0, sizeof(uint32_t), ctx->stream));
+    return VRS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrs_run_length_encode_scratch_bytes(uint32_t num_elements, int key_bytes, int flags, uint64_t *bytes) {
+    if (!bytes) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "bytes is NULL");
+    if (key_bytes != 4 && key_bytes != 8) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "run-length encode: key_bytes must be 4 or 8");
+    if (flags & ~kKnownRleFlags) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "run-length encode: unknown flag bits");
+    *bytes = vrs::rle_layout(num_elements, flags).bytes;
+    return VRS_OK;
+}
+
+int vrs_run_length_encode(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, int key_bytes, vrs_buffer out_keys, vrs_buffer out_offsets,
+                          vrs_buffer out_counts, vrs_buffer out_run_ids, vrs_buffer out_num_runs, vrs_buffer scratch) {
+    if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
+    if (key_bytes != 4 && key_bytes != 8) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "run-length encode: key_bytes must be 4 or 8");
+    if (!keys || !out_num_runs || !scratch) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
+    const uint32_t n = num_elements;
+    const size_t kb = static_cast<size_t>(n) * key_bytes, wb = static_cast<size_t>(n) * sizeof(uint32_t);
+    const vrs::RleLayout L = vrs::rle_layout(n, out_counts && !out_offsets ? vrs::kRleCounts : 0);
+    int rc;
+    if ((rc = check_buffer(ctx, keys, kb, "keys")) || (rc = check_buffer(ctx, out_num_runs, sizeof(uint32_t), "out_num_runs")) ||
+        (out_keys && (rc = check_buffer(ctx, out_keys, kb, "out_keys"))) ||
+        (out_offsets && (rc = check_buffer(ctx, out_offsets, wb + sizeof(uint32_t), "out_offsets"))) ||
+        (out_counts && (rc = check_buffer(ctx, out_counts, wb, "out_counts"))) ||
+        (out_run_ids && (rc = check_buffer(ctx, out_run_ids, wb, "out_run_ids"))) || (rc = check_buffer(ctx, scratch, L.bytes, "scratch")))
+        return rc;
+    VRS_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = settle_pending(ctx))) return rc;
+    if (n == 0u) return write_no_runs(ctx, out_num_runs);
+    char *s = static_cast<char *>(scratch->ptr);
+    vrs::RleArgs a{};
+    a.keys = keys->ptr;
+    a.n = n;
+    a.key_bytes = key_bytes;
+    a.key_type = -1;
+    a.idx = nullptr;
+    a.out_keys = out_keys ? out_keys->ptr : nullptr;
+    a.out_offsets = out_offsets ? static_cast<uint32_t *>(out_offsets->ptr) : out_counts ? reinterpret_cast<uint32_t *>(s + L.offsets) : nullptr;
+    a.out_counts = out_counts ? static_cast<uint32_t *>(out_counts->ptr) : nullptr;
+    a.out_run_ids = out_run_ids ? static_cast<uint32_t *>(out_run_ids->ptr) : nullptr;
+    a.out_num_runs = static_cast<uint32_t *>(out_num_runs->ptr);
+    a.status = s + L.status;
+    VRS_HIP(ctx, vrs::launch_rle(ctx->stream, a));
+    return VRS_OK;
+}
+
+int vrs_unique_scratch_bytes(uint32_t num_elements, int key_type, int flags, uint64_t *bytes) {
+    if (!bytes) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "bytes is NULL");
+    if (!known_key_type(key_type)) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "unique: unknown key_type");
+    if (flags & ~kKnownUniqueFlags) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "unique: unknown flag bits");
+    *bytes = vrs::unique_layout(num_elements, key_type, flags).bytes;
+    return VRS_OK;
+}
+
+int vrs_unique(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, int key_type, vrs_buffer out_keys, vrs_buffer out_counts,
+               vrs_buffer out_inverse, vrs_buffer out_num_runs, vrs_buffer scratch) {
+    if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
+    if (!known_key_type(key_type)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "unique: unknown key_type");
+    if (!keys || !out_keys || !out_num_runs || !scratch) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
+    const uint32_t n = num_elements;
+    const int kbytes = vrs::unique_key_bytes(key_type);
+    const size_t kb = static_cast<size_t>(n) * kbytes, wb = static_cast<size_t>(n) * sizeof(uint32_t);
+    const int flags = (out_inverse ? vrs::kUniqueInverse : 0) | (out_counts ? vrs::kUniqueCounts : 0);
+    const vrs::UniqueLayout L = vrs::unique_layout(n, key_type, flags);
+    int rc;
+    if ((rc = check_buffer(ctx, keys, kb, "keys")) || (rc = check_buffer(ctx, out_keys, kb, "out_keys")) ||
+        (rc = check_buffer(ctx, out_num_runs, sizeof(uint32_t), "out_num_runs")) ||
+        (out_counts && (rc = check_buffer(ctx, out_counts, wb, "out_counts"))) ||
+        (out_inverse && (rc = check_buffer(ctx, out_inverse, wb, "out_inverse"))) || (rc = check_buffer(ctx, scratch, L.bytes, "scratch")))
+        return rc;
+    VRS_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = settle_pending(ctx))) return rc;
+    if (n == 0u) return write_no_runs(ctx, out_num_runs);
+
+    // 1. ranks (and iota payloads) into the scratch; 2. the stable one-call sort on views of it, settled: everything it needs is on the
+    // stream (it may wait for its plan's head, never for the sort); 3. the encode over the sorted ranks
+    char *s = static_cast<char *>(scratch->ptr);
+    auto *vals = out_inverse ? reinterpret_cast<uint32_t *>(s + L.vals) : nullptr;
+    VRS_HIP(ctx, vrs::launch_unique_map(ctx->stream, keys->ptr, n, key_type, s + L.keys, vals));
+    vrs_buffer_t kv = stack_view(ctx, s + L.keys, kb), kt = stack_view(ctx, s + L.keys_tmp, kb);
+    vrs_buffer_t vv = stack_view(ctx, s + L.vals, wb), vt = stack_view(ctx, s + L.vals_tmp, wb);
+    if (kbytes == 8)
+        rc = out_inverse ? vrs_sort_pairs_u64(ctx, &kv, &kt, &vv, &vt, n) : vrs_sort_keys_u64(ctx, &kv, &kt, n);
+    else
+        rc = out_inverse ? vrs_sort_pairs_u32(ctx, &kv, &kt, &vv, &vt, n) : vrs_sort_keys_u32(ctx, &kv, &kt, n);
+    if (rc || (rc = settle_pending(ctx))) return rc;
+    vrs::RleArgs a{};
+    a.keys = s + L.keys;
+    a.n = n;
+    a.key_bytes = kbytes;
+    a.key_type = key_type;
+    a.idx = vals;
+    a.out_keys = out_keys->ptr;
+    a.out_offsets = out_counts ? reinterpret_cast<uint32_t *>(s + L.offsets) : nullptr;
+    a.out_counts = out_counts ? static_cast<uint32_t *>(out_counts->ptr) : nullptr;
+    a.out_run_ids = out_inverse ? static_cast<uint32_t *>(out_inverse->ptr) : nullptr;
+    a.out_num_runs = static_cast<uint32_t *>(out_num_runs->ptr);
+    a.status = s + L.status;
+    VRS_HIP(ctx, vrs::launch_rle(ctx->stream, a));
+    return VRS_OK;
+}
+
+}  // extern "C"

@@ -327,6 +327,47 @@ int vrs_segmented_stats(vrs_context ctx, uint64_t *wave_segments, uint64_t *bloc
  * one_call_min_keys: VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS (0 = never the one-call tier); *tier = VRS_SEGMENT_*. */
 int vrs_segment_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, int pairs, uint32_t one_call_min_keys,
                          int *tier, uint32_t *clamped_begin, uint32_t *clamped_end);
+/* 64-bit keys: the same contract as the uint32 forms above (offsets, clamping, untouched gaps, NULL and size checks -- keys and
+ * keys_tmp hold 8 * num_elements bytes, values and values_tmp 4 * num_elements --, blocking; the pairs form is stable).  Tiers: one
+ * wave per segment up to 896 elements, one workgroup sorting inside LDS up to 13312 keys / 6656 pairs (16 bytes of traffic per key,
+ * 24 per pair), one workgroup per segment through keys_tmp below VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS, and from there on
+ * vrs_sort_keys_u64 / vrs_sort_pairs_u64 on views of the buffers.  As in the uint32 forms only the bits that vary within a segment
+ * are sorted.  Their segments count in vrs_segmented_stats' four counters. */
+int vrs_sort_segments_u64(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, uint32_t num_elements,
+                          vrs_buffer offsets, uint32_t num_segments);
+int vrs_sort_segments_pairs_u64(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values /* uint32 */,
+                                vrs_buffer values_tmp, uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments);
+/* vrs_segment_tier_for with the 64-bit capacities (a pure function, needs no device) */
+int vrs_segment_tier_for_u64(uint32_t begin, uint32_t end, uint32_t num_elements, int pairs, uint32_t one_call_min_keys,
+                             int *tier, uint32_t *clamped_begin, uint32_t *clamped_end);
+
+/*
+ * torch.sort drop-in (build extension; no reference counterpart): the two streaming kernels around a stable segmented sort of ranks.
+ * A tensor is seen as num_elements / row_len rows of row_len elements (num_elements a whole number of rows).
+ * vrs_sort_rank_keys writes out_ranks[i] = r(src[i]) -- uint32 for every dtype of up to 4 bytes (the narrow ones zero-extended),
+ * uint64 for INT64 / FLOAT64 (vrs_sort_rank_bytes) -- and out_positions[i] = i mod row_len (uint32; may be NULL).  r is torch's order:
+ * unsigned as is, signed with the sign bit flipped, floats by the IEEE-754 total order except that -0.0 gets +0.0's rank and every NaN,
+ * whatever its sign or payload, the largest rank of its width; VRS_SORT_DESCENDING: ~r.  A stable ascending sort of the ranks (with
+ * the positions as payloads) is then torch.sort(x, dim=-1, descending, stable=True) of every row.
+ * vrs_sort_restore writes out_values from the sorted ranks by inverting r -- an element of the merged ±0.0 or NaN class reads its bits
+ * from src[row * row_len + position] -- and out_indices_i64[i] = positions[i] as int64.  Either output may be NULL; indices need
+ * positions, and the values of a float dtype need src and positions.  src is never written.
+ * NULL ctx or handles, an unknown dtype or flag bit, num_elements not a whole number of rows and undersized buffers:
+ * VRS_ERROR_INVALID_ARGUMENT before anything is enqueued; num_elements == 0: VRS_OK, nothing done.  Stream-ordered on the context's
+ * stream; both calls only enqueue (after settling a pending one-call sort).
+ */
+typedef enum vrs_sort_dtype {
+    VRS_SORT_INT8 = 0, VRS_SORT_UINT8 = 1, VRS_SORT_INT16 = 2, VRS_SORT_INT32 = 3, VRS_SORT_INT64 = 4,
+    VRS_SORT_FLOAT16 = 5, VRS_SORT_BFLOAT16 = 6, VRS_SORT_FLOAT32 = 7, VRS_SORT_FLOAT64 = 8
+} vrs_sort_dtype;
+enum { VRS_SORT_DESCENDING = 1 }; /* flags */
+int vrs_sort_rank_keys(vrs_context ctx, vrs_buffer src, uint32_t num_elements, uint32_t row_len, int dtype, int flags,
+                       vrs_buffer out_ranks /* uint32 or uint64 */, vrs_buffer out_positions /* uint32, may be NULL */);
+int vrs_sort_restore(vrs_context ctx, vrs_buffer src, vrs_buffer ranks, vrs_buffer positions /* may be NULL */,
+                     uint32_t num_elements, uint32_t row_len, int dtype, int flags,
+                     vrs_buffer out_values /* may be NULL */, vrs_buffer out_indices_i64 /* may be NULL */);
+/* the bytes of one rank of dtype: 4 or 8 (a pure function, needs no device) */
+int vrs_sort_rank_bytes(int dtype, int *rank_bytes);
 
 /*
  * Top-k selection (build extension; no reference counterpart): the k smallest (or largest) keys of every segment of one buffer and

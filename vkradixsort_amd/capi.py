@@ -77,6 +77,8 @@ SEGMENT_ONE_CALL_MIN_KEYS_DEFAULT = 1 << 20  # the library's default for VRS_TUN
 VRS_SEGMENT_WAVE, VRS_SEGMENT_BLOCK, VRS_SEGMENT_GLOBAL, VRS_SEGMENT_ONE_CALL = 0, 1, 2, 3
 SEGMENT_WAVE_MAX = 1789
 SEGMENT_BLOCK_MAX_KEYS, SEGMENT_BLOCK_MAX_PAIRS = 14333, 13312
+SEGMENT_WAVE_MAX_U64 = 896  # the 64-bit forms (vrs_sort_segments_u64 / _pairs_u64)
+SEGMENT_BLOCK_MAX_KEYS_U64, SEGMENT_BLOCK_MAX_PAIRS_U64 = 13312, 6656
 VRS_TUNE_TOPK_GRID_MIN_KEYS = 28
 TOPK_GRID_MIN_KEYS_DEFAULT = 1 << 17  # the library's default for VRS_TUNE_TOPK_GRID_MIN_KEYS
 # top-k selection: key types, flags, tiers (vrs_topk_tier) and the lengths that bound them
@@ -90,6 +92,10 @@ VRS_RLE_COUNTS = 1
 VRS_UNIQUE_U32, VRS_UNIQUE_I32, VRS_UNIQUE_F32, VRS_UNIQUE_U64, VRS_UNIQUE_I64, VRS_UNIQUE_F64 = 0, 1, 2, 3, 4, 5
 VRS_UNIQUE_INVERSE, VRS_UNIQUE_COUNTS = 1, 2
 RLE_TILE = 4096
+# the torch.sort drop-in's rank / restore kernels: dtypes (vrs_sort_dtype) and flags
+(VRS_SORT_INT8, VRS_SORT_UINT8, VRS_SORT_INT16, VRS_SORT_INT32, VRS_SORT_INT64, VRS_SORT_FLOAT16, VRS_SORT_BFLOAT16, VRS_SORT_FLOAT32,
+ VRS_SORT_FLOAT64) = range(9)
+VRS_SORT_DESCENDING = 1
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -217,6 +223,12 @@ _SIGNATURES = [
     ("vrs_sort_segments_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
     ("vrs_segmented_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_segment_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+    ("vrs_sort_segments_u64", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+    ("vrs_sort_segments_pairs_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+    ("vrs_segment_tier_for_u64", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+    ("vrs_sort_rank_keys", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p]),
+    ("vrs_sort_restore", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p]),
+    ("vrs_sort_rank_bytes", c_int, [c_int, POINTER(c_int)]),
     ("vrs_topk_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
     ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),

@@ -1,5 +1,6 @@
-// vrs_capi_segmented.hip -- the C ABI of the segmented sorts (vrs_sort_segments_*): argument checks, the context's work lists, the launches
-// of vrs_segmented.hip, and the one-call tier (segments too long for one workgroup, sorted by the one-call sort on views of the buffers).
+// vrs_capi_segmented.hip -- the C ABI of the segmented sorts (vrs_sort_segments_*, 32- and 64-bit keys): argument checks, the context's work
+// lists, the launches of vrs_segmented.hip, and the one-call tier (segments too long for one workgroup, sorted by the one-call sort on views
+// of the buffers).
 #include "vrs_host.hpp"
 #include "vrs_segmented.hpp"
 
@@ -35,25 +36,26 @@ namespace {
 uint32_t list_cap(uint32_t n, uint32_t num_segments, uint32_t shortest) { return std::min(num_segments, n / shortest); }
 
 int segmented(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values, vrs_buffer values_tmp, uint32_t n, vrs_buffer offsets,
-              uint32_t num_segments, bool pairs) {
+              uint32_t num_segments, bool pairs, int key_bytes) {
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
     if (!keys || !keys_tmp || !offsets || (pairs && (!values || !values_tmp)))
         return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
     if (n == 0u || num_segments == 0u) return VRS_OK;
-    const size_t bytes = static_cast<size_t>(n) * sizeof(uint32_t);
+    const size_t bytes = static_cast<size_t>(n) * sizeof(uint32_t), kbytes = static_cast<size_t>(n) * key_bytes;
     int rc;
-    if ((rc = check_buffer(ctx, keys, bytes, "keys")) || (rc = check_buffer(ctx, keys_tmp, bytes, "keys_tmp"))) return rc;
+    if ((rc = check_buffer(ctx, keys, kbytes, "keys")) || (rc = check_buffer(ctx, keys_tmp, kbytes, "keys_tmp"))) return rc;
     if (pairs && ((rc = check_buffer(ctx, values, bytes, "values")) || (rc = check_buffer(ctx, values_tmp, bytes, "values_tmp")))) return rc;
     if ((rc = check_buffer(ctx, offsets, (static_cast<size_t>(num_segments) + 1u) * sizeof(uint32_t), "offsets"))) return rc;
     VRS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = settle_pending(ctx))) return rc;
 
-    const uint32_t block_cap = pairs ? vrs::kSegBlockCapPairs : vrs::kSegBlockCapKeys;
+    const bool wide = key_bytes == 8;
+    const uint32_t block_cap = vrs::seg_block_cap(wide, pairs);
     const uint32_t min_keys = ctx->seg_one_call_min_keys;
     vrs::SegLists lists{};
     lists.cap[vrs::kSegListWaveSmall] = list_cap(n, num_segments, 2u);
     lists.cap[vrs::kSegListWave] = list_cap(n, num_segments, vrs::kSegWaveSmallCap + 1u);
-    lists.cap[vrs::kSegListBlockSmall] = list_cap(n, num_segments, vrs::kSegWaveCap + 1u);
+    lists.cap[vrs::kSegListBlockSmall] = list_cap(n, num_segments, vrs::seg_wave_cap(wide) + 1u);
     lists.cap[vrs::kSegListBlock] = list_cap(n, num_segments, vrs::kSegBlockSmallCap + 1u);
     const bool one_call = min_keys != 0u && n >= min_keys && n > block_cap;  // else no segment can reach the one-call tier
     const uint32_t global_max = one_call ? std::max(min_keys, block_cap + 1u) - 1u : n;  // longest segment of the global tier
@@ -107,10 +109,10 @@ int segmented(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer 
     for (int l = 0; l < vrs::kSegLists; ++l) grid[l] = lists.cap[l];
     if (++s->stamp == 0u) s->stamp = 1u;
     const uint32_t stamp = s->stamp;
-    auto *kp = static_cast<uint32_t *>(keys->ptr), *tp = static_cast<uint32_t *>(keys_tmp->ptr);
+    auto *kp = static_cast<char *>(keys->ptr), *tp = static_cast<char *>(keys_tmp->ptr);
     auto *vp = pairs ? static_cast<uint32_t *>(values->ptr) : nullptr, *vtp = pairs ? static_cast<uint32_t *>(values_tmp->ptr) : nullptr;
     VRS_HIP(ctx, vrs::launch_segmented(ctx->stream, kp, tp, vp, vtp, n, static_cast<const uint32_t *>(offsets->ptr), num_segments,
-                                       one_call ? min_keys : 0u, s->control, lists, grid, one_call ? s->host_dev : nullptr, stamp));
+                                       one_call ? min_keys : 0u, s->control, lists, grid, one_call ? s->host_dev : nullptr, stamp, key_bytes));
     if (!one_call) return VRS_OK;
 
     // the one-call tier: wait for the classification's list (never for the sorts), then one sort per segment on views of the buffers
@@ -120,10 +122,10 @@ int segmented(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer 
     std::vector<uint32_t> ranges(s->host + 2, s->host + 2 + 2u * static_cast<size_t>(count));
     for (uint32_t i = 0; i < count; ++i) {
         const uint32_t b = ranges[2u * i], len = ranges[2u * i + 1u] - b;
-        const size_t off = static_cast<size_t>(b), vb = static_cast<size_t>(len) * sizeof(uint32_t);
-        vrs_buffer_t k = stack_view(ctx, kp + off, vb), kt = stack_view(ctx, tp + off, vb);
+        const size_t off = static_cast<size_t>(b), vb = static_cast<size_t>(len) * sizeof(uint32_t), kb = static_cast<size_t>(len) * key_bytes;
+        vrs_buffer_t k = stack_view(ctx, kp + off * key_bytes, kb), kt = stack_view(ctx, tp + off * key_bytes, kb);
         vrs_buffer_t v = stack_view(ctx, pairs ? vp + off : nullptr, vb), vt = stack_view(ctx, pairs ? vtp + off : nullptr, vb);
-        if ((rc = sort_all_passes(ctx, &k, &kt, pairs ? &v : nullptr, pairs ? &vt : nullptr, len))) return rc;
+        if ((rc = sort_all_passes(ctx, &k, &kt, pairs ? &v : nullptr, pairs ? &vt : nullptr, len, key_bytes))) return rc;
     }
     return VRS_OK;
 }
@@ -134,12 +136,22 @@ extern "C" {
 
 int vrs_sort_segments_u32(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, uint32_t num_elements, vrs_buffer offsets,
                           uint32_t num_segments) {
-    return segmented(ctx, keys, keys_tmp, nullptr, nullptr, num_elements, offsets, num_segments, false);
+    return segmented(ctx, keys, keys_tmp, nullptr, nullptr, num_elements, offsets, num_segments, false, 4);
 }
 
 int vrs_sort_segments_pairs_u32(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values, vrs_buffer values_tmp,
                                 uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments) {
-    return segmented(ctx, keys, keys_tmp, values, values_tmp, num_elements, offsets, num_segments, true);
+    return segmented(ctx, keys, keys_tmp, values, values_tmp, num_elements, offsets, num_segments, true, 4);
+}
+
+int vrs_sort_segments_u64(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, uint32_t num_elements, vrs_buffer offsets,
+                          uint32_t num_segments) {
+    return segmented(ctx, keys, keys_tmp, nullptr, nullptr, num_elements, offsets, num_segments, false, 8);
+}
+
+int vrs_sort_segments_pairs_u64(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values, vrs_buffer values_tmp,
+                                uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments) {
+    return segmented(ctx, keys, keys_tmp, values, values_tmp, num_elements, offsets, num_segments, true, 8);
 }
 
 int vrs_segmented_stats(vrs_context ctx, uint64_t *wave_segments, uint64_t *block_segments, uint64_t *global_segments,
@@ -163,6 +175,13 @@ int vrs_segment_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, in
                          uint32_t *clamped_begin, uint32_t *clamped_end) {
     if (!tier || !clamped_begin || !clamped_end) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "an output pointer is NULL");
     *tier = vrs::segment_tier(begin, end, num_elements, pairs != 0, one_call_min_keys, clamped_begin, clamped_end);
+    return VRS_OK;
+}
+
+int vrs_segment_tier_for_u64(uint32_t begin, uint32_t end, uint32_t num_elements, int pairs, uint32_t one_call_min_keys, int *tier,
+                             uint32_t *clamped_begin, uint32_t *clamped_end) {
+    if (!tier || !clamped_begin || !clamped_end) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "an output pointer is NULL");
+    *tier = vrs::segment_tier(begin, end, num_elements, pairs != 0, one_call_min_keys, clamped_begin, clamped_end, true);
     return VRS_OK;
 }
 

@@ -486,7 +486,8 @@ __global__ __launch_bounds__(kThreads) void fold_histograms_kernel(const uint32_
 // ---------------------------------------------------------------------------------------------
 // Key preprocessing the reference leaves to the integrator ("you have to preprocess negative numbers",
 // README.md:154-155): order-preserving bijections between int32 / float32 bit patterns and the uint32
-// keys the sort orders.  In place, 16 bytes per lane, grid-stride.
+// keys the sort orders.  In place, 16 bytes per lane, grid-stride (64-bit indices, as in verify_keys_kernel: a 32-bit i + stride
+// would wrap below n near 2^32).
 //   mode 0  int32   <-> sortable : flip the sign bit (self-inverse)
 //   mode 1  float32  -> sortable : negative: flip all bits, else flip the sign bit (IEEE total order)
 //   mode 2  sortable -> float32  : inverse of mode 1
@@ -498,13 +499,13 @@ __device__ __forceinline__ uint32_t transform_key(uint32_t x, int mode) {
 
 __global__ __launch_bounds__(kThreads) void transform_keys_kernel(uint32_t *keys, uint32_t n, int mode) {
     if (reinterpret_cast<uintptr_t>(keys) & 15u) {  // sub-range of a larger allocation: plain 4-byte accesses
-        for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads)
+        for (size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * kThreads)
             keys[i] = transform_key(keys[i], mode);
         return;
     }
     uint4 *v = reinterpret_cast<uint4 *>(keys);
     const uint32_t nvec = n >> 2;
-    for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < nvec; i += gridDim.x * kThreads) {
+    for (size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; i < nvec; i += static_cast<size_t>(gridDim.x) * kThreads) {
         uint4 q = v[i];
         q.x = transform_key(q.x, mode);
         q.y = transform_key(q.y, mode);

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(1024) void segmented_global_sort_kernel(K *__restri
     for (int c = 0; c < DIGITS / 4; ++c) s_cnt[c * THREADS + tid] = 0u;
     if (tid < static_cast<uint32_t>(DIGITS)) s_same[tid] = 0u;
     __syncthreads();
-    for (uint32_t idx = tid; idx < n; idx += THREADS) {
+    for (size_t idx = tid; idx < n; idx += THREADS) {  // (64-bit here and below: a 32-bit idx + THREADS wraps below n near 2^32)
         const K k = keys[b + idx];
 #pragma unroll
         for (int j = 0; j < DIGITS; ++j) atomicAdd(&s_cnt[j * 256 + static_cast<uint32_t>((k >> (8 * j)) & 255u)], 1u);
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(1024) void segmented_global_sort_kernel(K *__restri
         K *kout = (cur ? keys : keys_tmp) + b;
         const uint32_t *vin = PAIRS ? (cur ? values_tmp : values) + b : nullptr;
         uint32_t *vout = PAIRS ? (cur ? values : values_tmp) + b : nullptr;
-        for (uint32_t t0 = 0; t0 < n; t0 += TILE) {
-            const uint32_t nt = min(static_cast<uint32_t>(TILE), n - t0);
+        for (uint64_t tile0 = 0; tile0 < n; tile0 += TILE) {
+            const uint32_t t0 = static_cast<uint32_t>(tile0), nt = min(static_cast<uint32_t>(TILE), n - t0);
             K key[ITEMS];
             uint32_t val[PAIRS ? ITEMS : 1];
 #pragma unroll
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(1024) void segmented_global_sort_kernel(K *__restri
         cur ^= 1u;
     }
     if (cur) {  // an odd number of passes: the result is in keys_tmp
-        for (uint32_t idx = tid; idx < n; idx += THREADS) {
+        for (size_t idx = tid; idx < n; idx += THREADS) {
             keys[b + idx] = keys_tmp[b + idx];
             if constexpr (PAIRS) values[b + idx] = values_tmp[b + idx];
         }

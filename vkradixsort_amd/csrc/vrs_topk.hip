@@ -12,6 +12,7 @@
 //   GRID tier: each phase one launch over a fixed grid that walks the tiles of every grid slot; per-workgroup LDS histograms flushed with
 //     one atomic per non-zero bin, one workgroup per slot picks the digit, a counting read and a per-slot scan order the emission.
 //   sorted output (k <= kTopkSortCap): one workgroup per segment sorts its survivors in LDS (local_pass, stable, over the bits that vary).
+// Loops whose bound may come near 2^32 (grid strides, a segment's tiles, k) count in 64 bits: a 32-bit i + step would wrap below the bound.
 #include "vrs_topk.hpp"
 
 #include "vrs_local_sort.hpp"
@@ -183,7 +184,7 @@ __device__ __forceinline__ uint2 emit_tile(Load load, uint32_t cnt, uint32_t pos
 }
 
 __device__ __forceinline__ void fill_tail(uint32_t *ok, uint32_t *oi, uint32_t m, uint32_t k, uint32_t threads) {
-    for (uint32_t j = m + threadIdx.x; j < k; j += threads) {
+    for (size_t j = m + threadIdx.x; j < k; j += threads) {
         ok[j] = 0xFFFFFFFFu;
         if (oi) oi[j] = 0xFFFFFFFFu;
     }
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(256) void topk_classify_kernel(TopkArgs a, TopkCont
         atomicAdd(&s_stat[tier], 1u);
         const uint32_t len = ce - cb, m = min(a.k, len);
         if (tier == kTopkTierGrid) {
-            const uint32_t tiles = (len + kTopkTile - 1u) / kTopkTile;
+            const uint32_t tiles = static_cast<uint32_t>((static_cast<uint64_t>(len) + kTopkTile - 1u) / kTopkTile);  // (len + 16383 wraps near 2^32)
             const unsigned long long old = atomicAdd(&ctl->grid_packed, (static_cast<unsigned long long>(tiles) << 32) | 1ull);
             const uint32_t slot = static_cast<uint32_t>(old), base = static_cast<uint32_t>(old >> 32);
             bool valid = false;
@@ -241,7 +242,8 @@ __global__ __launch_bounds__(THREADS) void topk_workgroup_kernel(TopkArgs a, con
     const uint32_t count = LDS ? ctl->lds_count : ctl->block_count;
     const bool largest = (a.flags & kTopkLargest) != 0;
     const int kt = a.key_type;
-    for (uint32_t j = blockIdx.x; j < count; j += gridDim.x) {
+    for (size_t jw = blockIdx.x; jw < count; jw += gridDim.x) {
+        const uint32_t j = static_cast<uint32_t>(jw);
         const uint32_t seg = LDS ? list[j] : list[a.num_segments - 1u - j];
         uint32_t b, e;
         (void)topk_tier(a.offsets[seg], a.offsets[seg + 1u], a.n, 0u, &b, &e);
@@ -259,8 +261,8 @@ __global__ __launch_bounds__(THREADS) void topk_workgroup_kernel(TopkArgs a, con
         for (int level = 0; level < kTopkLevels && !sel.done; ++level) {
             for (uint32_t c = threadIdx.x; c < kTopkBins; c += THREADS) s_hist[c] = 0u;
             __syncthreads();
-            for (uint32_t t0 = 0; t0 < len; t0 += TILE) {
-                const uint32_t cnt = min(static_cast<uint32_t>(TILE), len - t0);
+            for (uint64_t tile0 = 0; tile0 < len; tile0 += TILE) {  // (64-bit: a 32-bit t0 + TILE wraps below len near 2^32)
+                const uint32_t t0 = static_cast<uint32_t>(tile0), cnt = min(static_cast<uint32_t>(TILE), len - t0);
                 if constexpr (LDS) hist_tile<THREADS, ITEMS>([&](uint32_t p) { return s_r[t0 + p]; }, cnt, sel, level, s_hist);
                 else hist_tile<THREADS, ITEMS>([&](uint32_t p) { return topk_rank(src[t0 + p], kt, largest); }, cnt, sel, level, s_hist);
             }
@@ -270,8 +272,8 @@ __global__ __launch_bounds__(THREADS) void topk_workgroup_kernel(TopkArgs a, con
             __syncthreads();
         }
         uint32_t lt_base = 0, eq_base = 0;
-        for (uint32_t t0 = 0; t0 < len; t0 += TILE) {
-            const uint32_t cnt = min(static_cast<uint32_t>(TILE), len - t0);
+        for (uint64_t tile0 = 0; tile0 < len; tile0 += TILE) {
+            const uint32_t t0 = static_cast<uint32_t>(tile0), cnt = min(static_cast<uint32_t>(TILE), len - t0);
             uint2 tot;
             if constexpr (LDS)
                 tot = emit_tile<THREADS, ITEMS>([&](uint32_t p) { return s_r[t0 + p]; }, cnt, t0, sel, m, lt_base, eq_base, ok, oi, kt, largest, s_scan,
@@ -309,8 +311,8 @@ __device__ __forceinline__ uint32_t find_slot(const TopkSlot *slots, uint32_t ns
 
 __global__ __launch_bounds__(256) void topk_grid_init_kernel(const TopkControl *__restrict__ ctl, uint32_t *__restrict__ hist, uint32_t slot_cap) {
     const uint32_t ns = grid_slots(ctl, slot_cap);
-    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x)
-        for (uint32_t c = threadIdx.x; c < kTopkBins; c += 256u) hist[static_cast<size_t>(s) * kTopkBins + c] = 0u;
+    for (size_t s = blockIdx.x; s < ns; s += gridDim.x)
+        for (uint32_t c = threadIdx.x; c < kTopkBins; c += 256u) hist[s * kTopkBins + c] = 0u;
 }
 
 // PHASE 0: digit histograms of level `level`; 1: per-tile counts of the two classes; 2: the emission
@@ -342,7 +344,8 @@ __global__ __launch_bounds__(kGridThreads) void topk_grid_walk_kernel(TopkArgs a
         }
         __syncthreads();
     };
-    for (uint32_t t = blockIdx.x; t < total; t += gridDim.x) {
+    for (size_t tw = blockIdx.x; tw < total; tw += gridDim.x) {
+        const uint32_t t = static_cast<uint32_t>(tw);
         if (tid == 0u) s_slot = find_slot(slots, ns, t);
         __syncthreads();
         const uint32_t s = s_slot;
@@ -407,7 +410,8 @@ __global__ __launch_bounds__(256) void topk_grid_select_kernel(const TopkControl
     __shared__ uint32_t s_hist[kTopkBins];
     __shared__ uint32_t s_wtot[4], s_res[3];
     const uint32_t ns = grid_slots(ctl, slot_cap);
-    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x) {
+    for (size_t sw = blockIdx.x; sw < ns; sw += gridDim.x) {
+        const uint32_t s = static_cast<uint32_t>(sw);
         TopkSel sel = slots[s].sel;
         if (!slots[s].valid || sel.done) continue;
         uint32_t *h = hist + static_cast<size_t>(s) * kTopkBins;
@@ -429,7 +433,7 @@ __global__ __launch_bounds__(1024) void topk_grid_scan_kernel(TopkArgs a, const 
     __shared__ uint32_t s_wtot[2 * 16];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t ns = grid_slots(ctl, slot_cap);
-    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x) {
+    for (size_t s = blockIdx.x; s < ns; s += gridDim.x) {
         const TopkSlot sl = slots[s];
         if (!sl.valid) continue;
         fill_tail(a.out_keys + static_cast<size_t>(sl.seg) * a.k, a.out_indices ? a.out_indices + static_cast<size_t>(sl.seg) * a.k : nullptr, sl.m,
@@ -480,7 +484,8 @@ __global__ __launch_bounds__(THREADS) void topk_sort_small_kernel(TopkArgs a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t seg0 = wave * (ITEMS * 64) + lane;
     const bool largest = (a.flags & kTopkLargest) != 0;
-    for (uint32_t seg = blockIdx.x; seg < a.num_segments; seg += gridDim.x) {
+    for (size_t sw = blockIdx.x; sw < a.num_segments; sw += gridDim.x) {
+        const uint32_t seg = static_cast<uint32_t>(sw);
         uint32_t b, e;
         (void)topk_tier(a.offsets[seg], a.offsets[seg + 1u], a.n, 0u, &b, &e);
         const uint32_t m = min(a.k, e - b);
@@ -529,8 +534,8 @@ __device__ __forceinline__ uint32_t segment_m(const TopkArgs &a, uint32_t seg) {
 __global__ __launch_bounds__(256) void topk_sort_prep_kernel(TopkArgs a, uint32_t *__restrict__ sk, uint32_t *__restrict__ sv) {
     const uint32_t total = a.num_segments * a.k;
     const bool largest = (a.flags & kTopkLargest) != 0;
-    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < total; s += gridDim.x * 256u) {
-        const uint32_t seg = s / a.k, j = s - seg * a.k;
+    for (size_t sw = blockIdx.x * 256u + threadIdx.x; sw < total; sw += gridDim.x * 256u) {
+        const uint32_t s = static_cast<uint32_t>(sw), seg = s / a.k, j = s - seg * a.k;
         const bool in = j < segment_m(a, seg);
         sk[s] = in ? topk_rank(a.out_keys[s], a.key_type, largest) : 0xFFFFFFFFu;
         sv[s] = in && a.out_indices ? a.out_indices[s] : 0xFFFFFFFFu;
@@ -538,14 +543,14 @@ __global__ __launch_bounds__(256) void topk_sort_prep_kernel(TopkArgs a, uint32_
 }
 
 __global__ __launch_bounds__(256) void topk_sort_offsets_kernel(TopkArgs a) {
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= a.num_segments; i += gridDim.x * 256u) a.out_keys[i] = i * a.k;
+    for (size_t i = blockIdx.x * 256u + threadIdx.x; i <= a.num_segments; i += gridDim.x * 256u) a.out_keys[i] = static_cast<uint32_t>(i) * a.k;
 }
 
 __global__ __launch_bounds__(256) void topk_sort_back_kernel(TopkArgs a, const uint32_t *__restrict__ sk, const uint32_t *__restrict__ sv) {
     const uint32_t total = a.num_segments * a.k;
     const bool largest = (a.flags & kTopkLargest) != 0;
-    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < total; s += gridDim.x * 256u) {
-        const uint32_t seg = s / a.k, j = s - seg * a.k;
+    for (size_t sw = blockIdx.x * 256u + threadIdx.x; sw < total; sw += gridDim.x * 256u) {
+        const uint32_t s = static_cast<uint32_t>(sw), seg = s / a.k, j = s - seg * a.k;
         const bool in = j < segment_m(a, seg);
         a.out_keys[s] = in ? topk_unrank(sk[s], a.key_type, largest) : 0xFFFFFFFFu;
         if (a.out_indices) a.out_indices[s] = in ? sv[s] : 0xFFFFFFFFu;
@@ -596,7 +601,7 @@ hipError_t launch_topk_sort_prep(hipStream_t stream, const TopkArgs &a, const To
     const size_t sk = static_cast<size_t>(a.num_segments) * a.k;
     const uint32_t blocks = grid_of((sk + 255u) / 256u, 8192u);
     hipLaunchKernelGGL(topk_sort_prep_kernel, dim3(blocks), dim3(256), 0, stream, a, area, area + 2u * sk);
-    hipLaunchKernelGGL(topk_sort_offsets_kernel, dim3(grid_of((a.num_segments + 256u) / 256u, 8192u)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(topk_sort_offsets_kernel, dim3(grid_of((static_cast<uint64_t>(a.num_segments) + 256u) / 256u, 8192u)), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

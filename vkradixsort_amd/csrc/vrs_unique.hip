@@ -6,6 +6,7 @@
 //     Every element writes its run id, every head its run's key and start.
 //   rle_counts_kernel: counts[j] = offsets[j + 1] - offsets[j] for j < R, R read on the device; the grid is sized from n.
 //   unique_map_kernel: keys -> ranks (and the iota payloads the sort carries for the inverse).
+//   The grid-stride loops count in 64 bits: a 32-bit i + stride wraps to a small value still below a bound near 2^32 (a hang).
 #include "vrs_unique.hpp"
 
 #include <algorithm>
@@ -167,14 +168,14 @@ __global__ __launch_bounds__(kRleThreads) void rle_kernel(RleArgs a) {
 
 __global__ __launch_bounds__(256) void rle_counts_kernel(const uint32_t *offsets, const uint32_t *num_runs, uint32_t *counts) {
     const uint32_t R = *num_runs;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < R; j += gridDim.x * 256u) counts[j] = offsets[j + 1u] - offsets[j];
+    for (size_t j = blockIdx.x * 256u + threadIdx.x; j < R; j += gridDim.x * 256u) counts[j] = offsets[j + 1u] - offsets[j];
 }
 
 template <typename K>
 __global__ __launch_bounds__(256) void unique_map_kernel(const K *keys, uint32_t n, int key_type, K *mapped, uint32_t *vals) {
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+    for (size_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         mapped[i] = unique_rank(keys[i], key_type);
-        if (vals) vals[i] = i;
+        if (vals) vals[i] = static_cast<uint32_t>(i);
     }
 }
 

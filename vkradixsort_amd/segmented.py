@@ -90,4 +90,7 @@ def sort_rows(x, return_indices: bool = False):
     finally:
         for b in bufs:
             b.release()
-    return (out, idx.view(rows, length).long()) if return_indices else out
+    if not return_indices:
+        return out
+    pos = idx.view(rows, length).long()  # uint32 positions: an int32 view of them goes negative from 2^31 on
+    return out, (pos & 0xFFFFFFFF if length > 1 << 31 else pos)

@@ -94,4 +94,5 @@ def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
     finally:
         for b in bufs:
             b.release()
-    return values, idx.long()
+    # the positions are uint32: an int32 view of them goes negative from 2^31 on
+    return values, (idx.long() & 0xFFFFFFFF if length > 1 << 31 else idx.long())

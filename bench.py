@@ -7,12 +7,17 @@
 A step = one complete sort of one batch of synthetic keys that is already resident in HBM when the timed region starts.
 N = 1 times the library's one-call sort (vrs_sort_keys_u32; at 10^8 keys its hybrid form: one counting read, two MSD
 look-back scatter passes, the LDS-local bucket sort -- 28 B/key; below 1.3e7 keys the LSD form: one counting read + four
-look-back scatter passes, 36 B/key) and reports the reference's stage-by-stage contract path (4 x [histograms, prefix,
-scatter], 48 B/key) beside it; --path contract swaps the two.  N = 1 sorts BASELINE.json configs[2]: 10^8 uniform random
+look-back scatter passes, 36 B/key) and, with --full, reports the reference's stage-by-stage contract path (4 x [histograms,
+prefix, scatter], 48 B/key) beside it; --path contract swaps the two.  N = 1 sorts BASELINE.json configs[2]: 10^8 uniform random
 uint32 (std::mt19937 raw outputs, seeds 1/2/3 cycled over the K pre-staged batches); --n 1e7 is configs[1], --pairs
 configs[3] (key + payload pairs).  N > 1 sorts N x 10^8 keys sharded by key range (configs[4] at N = 8) through
 vrs_dist_sort_keys_u32: the hybrid sort with the RCCL all-to-all between its two MSD passes.  Rank 0 prints ONE JSON line.
 --dump-outputs DIR (N = 1) writes the arrays the timed path returned in its last step to DIR/<name>.npy (dump_outputs).
+
+A plain run sets up, warms up, times the K steps, checks their outputs on the device and prints the line.  --full runs on
+after the timed steps for everything else the line can report: the same steps again with no events and with every kernel
+timed, the other path over the same batches, the single-threaded std::sort baseline and the bit-exact check against it, the
+blocking and resampling variants, a device copy, and (N = 1, 10^8 keys) the `configs` block with configs[1] and configs[3].
 """
 from __future__ import annotations
 
@@ -291,6 +296,68 @@ def bench_single(args):
         dump_outputs(args.dump_outputs, {"sorted_keys": last})
         del last
 
+    if one_call and (hybrid_steps not in (0, K) or pool_steps not in (0, K) or pool_refused):
+        raise SystemExit(f"the timed steps mixed the forms of the one-call sort ({hybrid_steps} of {K} hybrid, {pool_steps} pool, {pool_refused} refused)")
+    hybrid = one_call and hybrid_steps == K
+    pool = hybrid and pool_steps == K
+    bytes_per_key_sort = {"one_call": BYTES_PER_KEY_SORT_POOL if pool else BYTES_PER_KEY_SORT_HYBRID if hybrid else BYTES_PER_KEY_SORT_ONE_READ,
+                          "contract": BYTES_PER_KEY_SORT}
+    dom_us = kernels.get(dominant_name, {}).get("avg_us")
+    dom_bytes = KERNEL_BYTES_PER_KEY.get(dominant_name, BYTES_PER_KEY_SCATTER) * n
+    traffic, traffic_detail = load_traffic_profile(dominant_name, dom_bytes) if n == 10 ** 8 else (None, {"note": "committed for N = 10^8 only"})
+    achieved = (dom_bytes / (dom_us * 1e-6) / 1e9) if dom_us else None
+    value = n * K / elapsed / 1e9
+    sort_bytes = bytes_per_key_sort[args.path] * n
+    shares = {x: round(r["launches"] * r["avg_us"], 1) for x, r in kernels.items() if x in KERNEL_BYTES_PER_KEY}
+    # the line of a plain run: the headline and what the timed region itself recorded
+    result = {
+        "metric": "Gkeys/s sorting 10^8 uint32 at 1/2/4/8 MI355X; % of HBM roofline",
+        "value": round(value, 3), "unit": "Gkeys/s", "n_gpus": 1, "steps": K, "warmup": W,
+        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": f"BASELINE.json configs[{ {10 ** 7: 1, 10 ** 8: 2}.get(n, 2) }]: {n} uniform random uint32 keys (std::mt19937 seeds 1,2,3), "
+                               f"multi_radixsort, 1xMI355X, keys resident in HBM",
+                   "path": pool_path_text(gpu.lib, n, tuned.get(capi.VRS_TUNE_MSD_POOL_TOP_BITS, 0)) if pool else
+                           (("vrs_sort_keys_u32, hybrid form: one counting read of the keys, an MSD partition by the top 14 bits in "
+                             "two stable scatter passes with decoupled look-back (8 + 6 bits), then every bucket sorted by its "
+                             "low 18 bits inside one workgroup's LDS (28 B/key); " + str(recount_steps) + " of the timed sorts "
+                             "needed a second counting read") if hybrid else
+                            ("vrs_sort_keys_u32: the library runs the four 8-bit passes itself -- one counting read of the "
+                             "keys, then four stable scatter passes with decoupled look-back (36 B/key)")) if one_call else
+                           ("MultiRadixSortPass stages, as MultiRadixSort::execute drives them: 4 x [histograms, prefix, "
+                            "scatter] with the caller-visible [W][256] table (48 B/key)"),
+                   "num_elements": n, "num_blocks_per_workgroup": B, "num_workgroups": Wg,
+                   "passes": "2 MSD scatter passes + 1 LDS-local sort pass" if hybrid else 4,
+                   "rank_mode": {1: "ballot", 2: "lds_atomic"}[gpu.lib.vrs_rank_mode(gpu.handle)], "device": dev_name,
+                   "compute_units": cus},
+        "roofline": {"bound": "hbm", "kernel": dominant_name, "kernel_is": KERNEL_WHAT.get(dominant_name),
+                     "chosen_by": "largest launches x average launch time among the byte-moving kernels whose launches carried events in the timed region",
+                     "instrumented_us_by_kernel": shares,
+                     "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
+                     "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": dom_us,
+                     "traffic": traffic, "traffic_detail": traffic_detail,
+                     "traffic_source": f"profiles/{dominant_name}_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                       "this command at N = 10^8 in an earlier run (counters cannot be read from inside this run); its "
+                                       "commit and box are in traffic_detail"},
+        "sort_roofline": {"algorithmic_bytes": sort_bytes, "bytes_per_key": bytes_per_key_sort[args.path],
+                          "achieved_GBps": round(sort_bytes * K / elapsed / 1e9, 1),
+                          "frac_of_peak": round(sort_bytes * K / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
+        "kernels_timed_region": kernels,
+        "kernels_timed_region_note": f"HIP events on the byte-moving kernels' launches of every {args.event_every}th step of the timed region",
+        "verified": {"timed_region_every_batch_ascending_and_permutation_of_its_input": True, "timed_region_batches_checked_on_device": K},
+    }
+
+    def release():
+        for b in batches + pristine + [buf1, hist]:
+            b.release()
+        p.release()
+        gpu.shutdown()
+
+    if not args.full:  # everything below runs outside the timed region, for --full alone
+        release()
+        return result
+
     # ---- outside the timed region: (a) the same K steps with no events at all (instrumentation overhead check),
     # (b) once more with every kernel timed, for the per-kernel breakdown
     rearm()
@@ -409,28 +476,17 @@ def bench_single(args):
         copy_times.append(time.perf_counter() - t0)
     copy_gbps = 2 * 4 * n / min(copy_times[1:]) / 1e9
 
-    if one_call and (hybrid_steps not in (0, K) or pool_steps not in (0, K) or pool_refused):
-        raise SystemExit(f"the timed steps mixed the forms of the one-call sort ({hybrid_steps} of {K} hybrid, {pool_steps} pool, {pool_refused} refused)")
-    hybrid = one_call and hybrid_steps == K
-    pool = hybrid and pool_steps == K
     other_pool = (not one_call) and other_hybrid and pool_sorts()[0] - pool_after[0] >= K
-    bytes_per_key_sort = {"one_call": BYTES_PER_KEY_SORT_POOL if (pool or other_pool) else BYTES_PER_KEY_SORT_HYBRID if (hybrid or other_hybrid)
-                          else BYTES_PER_KEY_SORT_ONE_READ,
-                          "contract": BYTES_PER_KEY_SORT}
-    dom_us = kernels.get(dominant_name, {}).get("avg_us")
-    dom_bytes = KERNEL_BYTES_PER_KEY.get(dominant_name, BYTES_PER_KEY_SCATTER) * n
-    traffic, traffic_detail = load_traffic_profile(dominant_name, dom_bytes) if n == 10 ** 8 else (None, {"note": "committed for N = 10^8 only"})
-    achieved = (dom_bytes / (dom_us * 1e-6) / 1e9) if dom_us else None
-    value = n * K / elapsed / 1e9
-    sort_bytes = bytes_per_key_sort[args.path] * n
+    if not one_call:
+        bytes_per_key_sort["one_call"] = (BYTES_PER_KEY_SORT_POOL if other_pool else BYTES_PER_KEY_SORT_HYBRID if other_hybrid
+                                          else BYTES_PER_KEY_SORT_ONE_READ)
     other_dom_name = pick_dominant(other_breakdown)
     other_dom_us = other_breakdown.get(other_dom_name, {}).get("avg_us")
-    shares = {x: round(r["launches"] * r["avg_us"], 1) for x, r in kernels.items() if x in KERNEL_BYTES_PER_KEY}
-    result = {
-        "metric": "Gkeys/s sorting 10^8 uint32 at 1/2/4/8 MI355X; % of HBM roofline",
-        "value": round(value, 3), "unit": "Gkeys/s", "n_gpus": 1, "steps": K, "warmup": W,
-        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+    result["roofline"].update({"measured_d2d_copy_GBps": round(copy_gbps, 1),
+                               "measured_d2d_copy_note": "hipMemcpyDtoD of one batch in this run, read + write bytes: what this box's "
+                                                         "HBM delivers for a mixed read/write stream, beside the 8 TB/s spec peak"})
+    result["verified"] = dict(check, **result["verified"])
+    result.update({
         "ms_per_step_individually_timed": {"min": round(min(singles), 4), "median": round(float(np.median(singles)), 4),
                                            "max": round(max(singles), 4),
                                            "note": "K further steps, each bracketed by a queue-idle wait (outside the timed region)"},
@@ -442,39 +498,6 @@ def bench_single(args):
         "every_sort_samples_note": "VRS_TUNE_MSD_POOL_REUSE_LAYOUT = 0: no sort starts in the regions an earlier one laid out (the timed region's sorts after the "
                                    "first do: a steady workload's gain); same batches back to back, outside the timed region",
         "changing_inputs": changing,
-        "config": {"workload": f"BASELINE.json configs[{ {10 ** 7: 1, 10 ** 8: 2}.get(n, 2) }]: {n} uniform random uint32 keys (std::mt19937 seeds 1,2,3), "
-                               f"multi_radixsort, 1xMI355X, keys resident in HBM",
-                   "path": pool_path_text(gpu.lib, n, tuned.get(capi.VRS_TUNE_MSD_POOL_TOP_BITS, 0)) if pool else
-                           (("vrs_sort_keys_u32, hybrid form: one counting read of the keys, an MSD partition by the top 14 bits in "
-                             "two stable scatter passes with decoupled look-back (8 + 6 bits), then every bucket sorted by its "
-                             "low 18 bits inside one workgroup's LDS (28 B/key); " + str(recount_steps) + " of the timed sorts "
-                             "needed a second counting read") if hybrid else
-                            ("vrs_sort_keys_u32: the library runs the four 8-bit passes itself -- one counting read of the "
-                             "keys, then four stable scatter passes with decoupled look-back (36 B/key)")) if one_call else
-                           ("MultiRadixSortPass stages, as MultiRadixSort::execute drives them: 4 x [histograms, prefix, "
-                            "scatter] with the caller-visible [W][256] table (48 B/key)"),
-                   "num_elements": n, "num_blocks_per_workgroup": B, "num_workgroups": Wg,
-                   "passes": "2 MSD scatter passes + 1 LDS-local sort pass" if hybrid else 4,
-                   "rank_mode": {1: "ballot", 2: "lds_atomic"}[gpu.lib.vrs_rank_mode(gpu.handle)], "device": dev_name,
-                   "compute_units": cus},
-        "roofline": {"bound": "hbm", "kernel": dominant_name, "kernel_is": KERNEL_WHAT.get(dominant_name),
-                     "chosen_by": "largest launches x average launch time among the byte-moving kernels whose launches carried events in the timed region",
-                     "instrumented_us_by_kernel": shares,
-                     "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
-                     "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": dom_us,
-                     "traffic": traffic, "traffic_detail": traffic_detail,
-                     "traffic_source": f"profiles/{dominant_name}_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                       "this command at N = 10^8 in an earlier run (counters cannot be read from inside this run); its "
-                                       "commit and box are in traffic_detail",
-                     "measured_d2d_copy_GBps": round(copy_gbps, 1),
-                     "measured_d2d_copy_note": "hipMemcpyDtoD of one batch in this run, read + write bytes: what this box's "
-                                               "HBM delivers for a mixed read/write stream, beside the 8 TB/s spec peak"},
-        "sort_roofline": {"algorithmic_bytes": sort_bytes, "bytes_per_key": bytes_per_key_sort[args.path],
-                          "achieved_GBps": round(sort_bytes * K / elapsed / 1e9, 1),
-                          "frac_of_peak": round(sort_bytes * K / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
-        "kernels_timed_region": kernels,
-        "kernels_timed_region_note": f"HIP events on the byte-moving kernels' launches of every {args.event_every}th step of the timed region",
         "kernels_all_instrumented_rerun": breakdown,
         "roofline_by_kernel": {name: {"algorithmic_bytes_per_launch": bpk * n, "avg_launch_us": breakdown[name]["avg_us"],
                                       "frac": round(bpk * n / (breakdown[name]["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
@@ -491,15 +514,10 @@ def bench_single(args):
                                 "frac": round(KERNEL_BYTES_PER_KEY[other_dom_name] * n / (other_dom_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
                                 if other_dom_us else None},
             "kernels": other_breakdown, "note": "same batches, uninstrumented timing; not the headline"},
-        "verified": dict(check, timed_region_every_batch_ascending_and_permutation_of_its_input=True,
-                         timed_region_batches_checked_on_device=K),
-    }
+    })
     if base:
         result["cpu_baseline"] = base
-    for b in batches + pristine + [buf1, hist]:
-        b.release()
-    p.release()
-    gpu.shutdown()
+    release()
     return result
 
 
@@ -593,6 +611,53 @@ def bench_pairs(args):
         vals[K - 1].downloadWithStagingBuffer(lv)
         dump_outputs(args.dump_outputs, {"sorted_keys": lk, "sorted_payloads": lv})
         del lk, lv
+    if hybrid_steps not in (0, K):
+        raise SystemExit(f"the timed steps mixed the two forms of the one-call sort ({hybrid_steps} of {K} hybrid)")
+    if pool_steps not in (0, K):
+        raise SystemExit(f"the timed steps mixed the pool and the counted form ({pool_steps} of {K} pool)")
+    hybrid, pool = hybrid_steps == K, pool_steps == K
+    # counting read 4 + (2 MSD passes + local sort | 4 LSD passes) x (read 8 + write 8); the pool form has no counting read
+    bpp = 48 if pool else 52 if hybrid else 68
+    pair_bytes = {"digit_tables": 4, "lookback_scatter": 16, "local_sort": 16, "pool_pass_a": 16, "pool_pass_b": 16}
+    dom_name = pick_dominant({k_: v for k_, v in kernels.items() if k_ in pair_bytes})
+    dom_us = kernels.get(dom_name, {}).get("avg_us")
+    dom_bytes = pair_bytes.get(dom_name, 16) * n
+    achieved = dom_bytes / (dom_us * 1e-6) / 1e9 if dom_us else None
+    traffic_name = "lookback_scatter_pairs" if dom_name == "lookback_scatter" else f"{dom_name}_pairs"
+    # the line of a plain run: the headline and what the timed region itself recorded
+    result = {
+        "metric": "Gkeys/s sorting 10^8 uint32 at 1/2/4/8 MI355X; % of HBM roofline",
+        "value": round(n * K / elapsed / 1e9, 3), "unit": "Gkeys/s", "n_gpus": 1, "steps": K, "warmup": W,
+        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u32", "data": "synthetic",
+        "config": {"workload": f"BASELINE.json configs[3]: {n} uint32 key + uint32 payload pairs (keys: std::mt19937 seeds 1,2,3; payload = "
+                               "input position), 1xMI355X, resident in HBM; every key counts once (a pair per key)",
+                   "path": pool_path_text(gpu.lib, n, 0, pairs=True) if pool else
+                           ("vrs_sort_pairs_u32, hybrid form: one counting read of the keys, two stable MSD scatter passes with decoupled "
+                            "look-back (keys + payloads), LDS-local bucket sort -- 52 B/pair") if hybrid else
+                           "vrs_sort_pairs_u32: one counting read + four stable look-back scatter passes -- 68 B/pair",
+                   "num_elements": n, "device": dev_name, "compute_units": cus},
+        "roofline": {"bound": "hbm", "kernel": dom_name, "kernel_is": (KERNEL_WHAT.get(dom_name) or "") + " -- here with payloads: every key and payload read and written once per launch",
+                     "chosen_by": "largest launches x average launch time among the byte-moving kernels whose launches carried events in the timed region",
+                     "instrumented_us_by_kernel": {x: round(r["launches"] * r["avg_us"], 1) for x, r in kernels.items() if x in pair_bytes},
+                     "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None, "algorithmic_bytes_per_launch": dom_bytes,
+                     "avg_launch_us": dom_us, "traffic": load_traffic_profile(traffic_name, float(dom_bytes))[0] if n == 10 ** 8 else None,
+                     "traffic_source": f"profiles/{traffic_name}_traffic.json (rocprofv3 --pmc passes of an earlier run of this command)"},
+        "sort_roofline": {"algorithmic_bytes": bpp * n, "bytes_per_key": bpp, "achieved_GBps": round(bpp * n * K / elapsed / 1e9, 1),
+                          "frac_of_peak": round(bpp * n * K / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
+        "kernels_timed_region": kernels,
+        "verified": {"timed_region_every_batch_keys_ascending_and_permutations": True, "timed_region_batches_checked_on_device": K},
+    }
+
+    def release():
+        for b in keys + vals + pristine + [pristine_vals, ktmp, vtmp]:
+            b.release()
+        gpu.shutdown()
+
+    if not args.full:  # everything below runs outside the timed region, for --full alone
+        release()
+        return result
     # bit for bit against std::stable_sort (keys AND payloads) for the first batch of every seed; its time is the CPU baseline
     base = None
     exact = None
@@ -618,50 +683,12 @@ def bench_pairs(args):
     unprofiled, _ = run_steps(K, 0)
     rearm()
     _, breakdown = run_steps(K, (1 << capi.VRS_KERNEL_COUNT) - 1)
-    if hybrid_steps not in (0, K):
-        raise SystemExit(f"the timed steps mixed the two forms of the one-call sort ({hybrid_steps} of {K} hybrid)")
-    if pool_steps not in (0, K):
-        raise SystemExit(f"the timed steps mixed the pool and the counted form ({pool_steps} of {K} pool)")
-    hybrid, pool = hybrid_steps == K, pool_steps == K
-    # counting read 4 + (2 MSD passes + local sort | 4 LSD passes) x (read 8 + write 8); the pool form has no counting read
-    bpp = 48 if pool else 52 if hybrid else 68
-    pair_bytes = {"digit_tables": 4, "lookback_scatter": 16, "local_sort": 16, "pool_pass_a": 16, "pool_pass_b": 16}
-    dom_name = pick_dominant({k_: v for k_, v in kernels.items() if k_ in pair_bytes})
-    dom_us = kernels.get(dom_name, {}).get("avg_us")
-    dom_bytes = pair_bytes.get(dom_name, 16) * n
-    achieved = dom_bytes / (dom_us * 1e-6) / 1e9 if dom_us else None
-    traffic_name = "lookback_scatter_pairs" if dom_name == "lookback_scatter" else f"{dom_name}_pairs"
-    result = {
-        "metric": "Gkeys/s sorting 10^8 uint32 at 1/2/4/8 MI355X; % of HBM roofline",
-        "value": round(n * K / elapsed / 1e9, 3), "unit": "Gkeys/s", "n_gpus": 1, "steps": K, "warmup": W,
-        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u32", "data": "synthetic",
-        "config": {"workload": f"BASELINE.json configs[3]: {n} uint32 key + uint32 payload pairs (keys: std::mt19937 seeds 1,2,3; payload = "
-                               "input position), 1xMI355X, resident in HBM; every key counts once (a pair per key)",
-                   "path": pool_path_text(gpu.lib, n, 0, pairs=True) if pool else
-                           ("vrs_sort_pairs_u32, hybrid form: one counting read of the keys, two stable MSD scatter passes with decoupled "
-                            "look-back (keys + payloads), LDS-local bucket sort -- 52 B/pair") if hybrid else
-                           "vrs_sort_pairs_u32: one counting read + four stable look-back scatter passes -- 68 B/pair",
-                   "num_elements": n, "device": dev_name, "compute_units": cus},
-        "roofline": {"bound": "hbm", "kernel": dom_name, "kernel_is": (KERNEL_WHAT.get(dom_name) or "") + " -- here with payloads: every key and payload read and written once per launch",
-                     "chosen_by": "largest launches x average launch time among the byte-moving kernels whose launches carried events in the timed region",
-                     "instrumented_us_by_kernel": {x: round(r["launches"] * r["avg_us"], 1) for x, r in kernels.items() if x in pair_bytes},
-                     "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None, "algorithmic_bytes_per_launch": dom_bytes,
-                     "avg_launch_us": dom_us, "traffic": load_traffic_profile(traffic_name, float(dom_bytes))[0] if n == 10 ** 8 else None,
-                     "traffic_source": f"profiles/{traffic_name}_traffic.json (rocprofv3 --pmc passes of an earlier run of this command)"},
-        "sort_roofline": {"algorithmic_bytes": bpp * n, "bytes_per_key": bpp, "achieved_GBps": round(bpp * n * K / elapsed / 1e9, 1),
-                          "frac_of_peak": round(bpp * n * K / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
-        "kernels_timed_region": kernels, "kernels_all_instrumented_rerun": breakdown,
-        "ms_per_step_uninstrumented_rerun": round(unprofiled / K * 1e3, 4),
-        "verified": {"timed_region_every_batch_keys_ascending_and_permutations": True, "timed_region_batches_checked_on_device": K,
-                     "bit_exact_vs_std_stable_sort_seeds": exact},
-    }
+    result["kernels_all_instrumented_rerun"] = breakdown
+    result["ms_per_step_uninstrumented_rerun"] = round(unprofiled / K * 1e3, 4)
+    result["verified"]["bit_exact_vs_std_stable_sort_seeds"] = exact
     if base:
         result["cpu_baseline"] = base
-    for b in keys + vals + pristine + [pristine_vals, ktmp, vtmp]:
-        b.release()
-    gpu.shutdown()
+    release()
     return result
 
 
@@ -802,7 +829,7 @@ def bench_multi_python(args, fallback_reason=None):
         sort_bpk = 28 if passes_per_range <= 2.5 else 36
         step_bpk = 12 + sort_bpk
         base = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from tests import _oracle
             orc = _oracle.load()
             sample = shard[:min(n, 2 * 10 ** 7)]
@@ -1182,7 +1209,7 @@ def bench_multi(args, fabric=None):
         own_in_place = grouped and pool_finish and os.environ.get("VRS_DIST_COPY_OWN") != "1"
         xchg_bpk = round(8.0 * (world - 1) / world, 2) if own_in_place else 8
         base = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from tests import _oracle
             orc = _oracle.load()
             sample = shard[:min(n, 2 * 10 ** 7)]
@@ -1248,7 +1275,7 @@ def bench_multi(args, fabric=None):
 
 
 def other_configs(args):
-    """The default line's `configs` block: BASELINE.json configs[1] (10^7 keys) and configs[3] (10^8 key + payload pairs) run the
+    """The --full line's `configs` block: BASELINE.json configs[1] (10^7 keys) and configs[3] (10^8 key + payload pairs) run the
     same way as the headline -- pre-staged batches, back-to-back steps, every output verified on the device, the first batch of every
     seed bit for bit against std::sort / std::stable_sort -- in short form (their full lines: --n 1e7 / --pairs)."""
     import copy
@@ -1287,8 +1314,11 @@ def main():
     ap.add_argument("--variant", type=int, default=0, help="scatter variant code (tuning)")
     ap.add_argument("--rounds", type=int, default=4, help="multi-GPU: sub-ranges per rank (exchange/sort pipelining)")
     ap.add_argument("--rounds-forced", action="store_true", help="use --rounds even at world size 1 (testing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="N = 1, default workload: leave out the `configs` block (10^7 keys, 10^8 pairs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the line reports: the reruns, the other path, the CPU baseline and the "
+                         "bit-exact check against it, the device copy, the `configs` block (without it the run stops after the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline and the bit-exact check against it")
+    ap.add_argument("--no-configs", action="store_true", help="--full, N = 1, default workload: leave out the `configs` block (10^7 keys, 10^8 pairs)")
     ap.add_argument("--loopback-ranks", type=int, default=0,
                     help="the multi-GPU step with this many ranks as THREADS of one process over the library's in-process transport "
                          "(one GPU: all ranks share it -- exercises every rank-to-rank path, measures no scaling)")
@@ -1339,7 +1369,7 @@ def main():
     result = bench_pairs(args) if args.pairs else bench_single(args)
     if result is not None and args.tune:
         result["config"]["lab_tunings"] = list(args.tune)  # (not the default line)
-    if result is not None and not args.pairs and args.n == 10 ** 8 and args.path == "one_call" and not args.no_configs:
+    if result is not None and args.full and not args.pairs and args.n == 10 ** 8 and args.path == "one_call" and not args.no_configs:
         result["configs"] = other_configs(args)
     if result is not None:
         print(json.dumps(result), flush=True)

@@ -288,7 +288,7 @@ def test_bench_multi_path_at_world_eight_over_the_loopback_transport():
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    p = subprocess.run([sys.executable, str(root / "bench.py"), "--loopback-ranks", "8", "--n", "2e6", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--loopback-ranks", "8", "--n", "2e6", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,7 @@ export TMPDIR=/tmp
 # usage: tools/lab/lds_pmc.sh [TAG]   (VRS_PMC_CMD: the command to profile instead of the bench, e.g. a lab build through tools/lab/ab_bench.py)
 TAG=${1:-lds_pmc}
 OUT=$PWD/gpurun_out/$TAG; rm -rf $OUT; mkdir -p $OUT
-CMD=${VRS_PMC_CMD:-"python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs"}
+CMD=${VRS_PMC_CMD:-"python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs"}
 for set in "SQ_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_INSTS_LDS" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "GRBM_GUI_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_ATOMIC_RETURN"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-40)
   timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/$tag -o b -- $CMD > /dev/null 2> $OUT/$tag.log || echo "failed $set"

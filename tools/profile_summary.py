@@ -55,7 +55,7 @@ def pick_dominant(rows, match):
 
 def dominant_records(rows, pairs=False):
     """file name -> record; the first MSD pass and the second are separate records of one file (bench.py reports both)"""
-    src = "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --steps 10 --warmup 2 --no-cpu-baseline`"
+    src = "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline`"
     corr = "FETCH_SIZE x2 (gfx950 counts 128-B requests at 64 B), WRITE_SIZE x1; both x1024 B"
     files = {}
     rec = pick_dominant(rows, lambda k: "scatter_kernel" in k and "onesweep" not in k)

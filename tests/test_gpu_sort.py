@@ -126,7 +126,7 @@ def test_row_lengths_at_one_call_threshold(dtype, length):
 
 
 def test_global_tier_counts():
-    ctx = vrs.segmented._context_for(torch, DEV)
+    ctx = vrs._torch.context_for(DEV)
     before = vrs.segmented_stats(ctx)
     g = torch.Generator().manual_seed(5)
     x = torch.randint(-(1 << 40), 1 << 40, (8, 1 << 17), generator=g, dtype=torch.int64).to(DEV)

@@ -275,7 +275,7 @@ def test_1e8_one_segment_default_tuning(largest):
     order = ref_segment(rank(keys, "f32", largest), k)
     assert np.array_equal(i.cpu().numpy(), order)
     assert np.array_equal(v.cpu().numpy().view(np.uint32), keys[order])
-    ctx = vrs.segmented._context_for(torch, x.device)
+    ctx = vrs._torch.context_for(x.device)
     assert vrs.topk_stats(ctx)["grid"] >= 1
 
 

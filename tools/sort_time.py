@@ -87,7 +87,7 @@ def main() -> int:
 
     import vkradixsort_amd as vrs
     from vkradixsort_amd import capi
-    from vkradixsort_amd.segmented import _context_for
+    from vkradixsort_amd._torch import context_for
 
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(1)
@@ -123,7 +123,7 @@ def main() -> int:
         torch.cuda.empty_cache()
 
     if not args.no_sweep:
-        ctx = _context_for(torch, dev)
+        ctx = context_for(dev)
         total = 1 << 24
         try:
             for L in (1 << 17, 1 << 18, 1 << 19, 1 << 20, 1 << 21, 1 << 22):

@@ -70,11 +70,11 @@ def main() -> int:
 
     import vkradixsort_amd as vrs
     from vkradixsort_amd import capi
-    from vkradixsort_amd.segmented import _context_for
+    from vkradixsort_amd._torch import context_for
 
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(1)
-    ctx = _context_for(torch, dev)
+    ctx = context_for(dev)
     results = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "scale": args.scale,
                "grid_min_keys": capi.TOPK_GRID_MIN_KEYS_DEFAULT, "cases": []}
     for name in args.cases:

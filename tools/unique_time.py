@@ -71,7 +71,7 @@ def main() -> int:
 
     import vkradixsort_amd as vrs
     from vkradixsort_amd import engine
-    from vkradixsort_amd.segmented import _context_for
+    from vkradixsort_amd._torch import context_for
 
     uq = importlib.import_module("vkradixsort_amd.unique")
 
@@ -102,7 +102,7 @@ def main() -> int:
                 torch.cuda.empty_cache()
 
     # the encode kernel alone over sorted keys: bytes it must move over the time, against the copy rate
-    ctx = _context_for(torch, dev)
+    ctx = context_for(dev)
     S = engine.Buffer.BufferSettings
     n = max(sizes)
     for dtype, kb in ((torch.int32, 4), (torch.int64, 8)):

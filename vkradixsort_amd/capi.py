@@ -290,6 +290,13 @@ def check(ctx_handle, rc: int) -> None:
         raise VrsError(rc, msg.decode() if msg else "unknown error")
 
 
+def query_u64(name: str, *args) -> int:
+    """The uint64 that the no-device query `name` (a *_scratch_bytes function) writes after its arguments; raises VrsError on failure."""
+    out = ctypes.c_uint64()
+    check(None, getattr(load_library(), name)(*args, ctypes.byref(out)))
+    return out.value
+
+
 def device_count() -> int:
     n = c_int(0)
     rc = load_library().vrs_device_count(byref(n))

@@ -67,10 +67,7 @@ int segmented(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer 
     if (!ctx->seg) ctx->seg = new (std::nothrow) vrs_segmented_state;
     vrs_segmented_state *s = ctx->seg;
     if (!s) return fail(ctx, VRS_ERROR_OUT_OF_MEMORY, "segmented sort state");
-    if (!s->control) {
-        VRS_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->control), sizeof(vrs::SegControl)));
-        VRS_HIP(ctx, hipMemsetAsync(s->control, 0, sizeof(vrs::SegControl), ctx->stream));
-    }
+    if ((rc = make_counters(ctx, &s->control, 1))) return rc;
     if (entries > s->list_entries) {
         if (s->lists) {
             VRS_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier segmented sort may still read them)
@@ -157,13 +154,8 @@ int vrs_sort_segments_pairs_u64(vrs_context ctx, vrs_buffer keys, vrs_buffer key
 int vrs_segmented_stats(vrs_context ctx, uint64_t *wave_segments, uint64_t *block_segments, uint64_t *global_segments,
                         uint64_t *one_call_segments) {
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
-    unsigned long long st[4] = {0, 0, 0, 0};
-    if (ctx->seg && ctx->seg->control) {
-        VRS_HIP(ctx, hipSetDevice(ctx->device));
-        if (const int rc = settle_pending(ctx)) return rc;
-        VRS_HIP(ctx, hipMemcpyAsync(st, ctx->seg->control->stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-        VRS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    unsigned long long st[4];
+    if (const int rc = read_counters(ctx, ctx->seg && ctx->seg->control ? ctx->seg->control->stats : nullptr, st, 4)) return rc;
     if (wave_segments) *wave_segments = st[vrs::kSegTierWave];
     if (block_segments) *block_segments = st[vrs::kSegTierBlock];
     if (global_segments) *global_segments = st[vrs::kSegTierGlobal];

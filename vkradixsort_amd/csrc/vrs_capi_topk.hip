@@ -52,13 +52,8 @@ int vrs_topk_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, uint3
 
 int vrs_topk_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments) {
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
-    unsigned long long st[3] = {0, 0, 0};
-    if (ctx->topk && ctx->topk->stats) {
-        VRS_HIP(ctx, hipSetDevice(ctx->device));
-        if (const int rc = settle_pending(ctx)) return rc;
-        VRS_HIP(ctx, hipMemcpyAsync(st, ctx->topk->stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-        VRS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    unsigned long long st[3];
+    if (const int rc = read_counters(ctx, ctx->topk ? ctx->topk->stats : nullptr, st, 3)) return rc;
     if (lds_segments) *lds_segments = st[vrs::kTopkTierLds];
     if (block_segments) *block_segments = st[vrs::kTopkTierBlock];
     if (grid_segments) *grid_segments = st[vrs::kTopkTierGrid];
@@ -86,10 +81,7 @@ int vrs_topk_segments(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, v
     if (!ctx->topk) ctx->topk = new (std::nothrow) vrs_topk_state;
     vrs_topk_state *s = ctx->topk;
     if (!s) return fail(ctx, VRS_ERROR_OUT_OF_MEMORY, "top-k state");
-    if (!s->stats) {
-        VRS_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->stats), 3 * sizeof(unsigned long long)));
-        VRS_HIP(ctx, hipMemsetAsync(s->stats, 0, 3 * sizeof(unsigned long long), ctx->stream));
-    }
+    if ((rc = make_counters(ctx, &s->stats, 3))) return rc;
     vrs::TopkArgs a{};
     a.keys = static_cast<const uint32_t *>(keys->ptr);
     a.offsets = static_cast<const uint32_t *>(offsets->ptr);

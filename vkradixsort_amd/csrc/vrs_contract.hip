@@ -17,6 +17,7 @@
 //                         LDS re-bucketing, then digit-contiguous global stores.  Stable.
 //   K4 single_kernel      the single_radixsort path: four passes inside one workgroup.
 #include "vrs_device.hpp"
+#include "vrs_key_order.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -486,15 +487,12 @@ __global__ __launch_bounds__(kThreads) void fold_histograms_kernel(const uint32_
 // ---------------------------------------------------------------------------------------------
 // Key preprocessing the reference leaves to the integrator ("you have to preprocess negative numbers",
 // README.md:154-155): order-preserving bijections between int32 / float32 bit patterns and the uint32
-// keys the sort orders.  In place, 16 bytes per lane, grid-stride (64-bit indices, as in verify_keys_kernel: a 32-bit i + stride
-// would wrap below n near 2^32).
-//   mode 0  int32   <-> sortable : flip the sign bit (self-inverse)
-//   mode 1  float32  -> sortable : negative: flip all bits, else flip the sign bit (IEEE total order)
-//   mode 2  sortable -> float32  : inverse of mode 1
+// keys the sort orders (vrs_key_order.hpp): mode 0 int32 <-> sortable, 1 float32 -> sortable, 2 sortable -> float32.  In place, 16
+// bytes per lane, grid-stride (64-bit indices, as in verify_keys_kernel: a 32-bit i + stride would wrap below n near 2^32).
 __device__ __forceinline__ uint32_t transform_key(uint32_t x, int mode) {
-    if (mode == 0) return x ^ 0x80000000u;
-    if (mode == 1) return x ^ ((x & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
-    return x ^ ((x & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu);
+    if (mode == 0) return key_from_signed(x);
+    if (mode == 1) return key_from_float(x);
+    return float_from_key(x);
 }
 
 __global__ __launch_bounds__(kThreads) void transform_keys_kernel(uint32_t *keys, uint32_t n, int mode) {

@@ -247,6 +247,26 @@ int one_read_settle(vrs_context ctx);
 int settle_pending(vrs_context ctx);
 void segmented_release(vrs_context ctx);
 void topk_release(vrs_context ctx);
+
+// A context's cumulative device counters (count entries of T): made and zeroed on its stream at first use; read back once the calls
+// before have finished (all zeros when they were never made: counters == NULL).
+template <typename T>
+int make_counters(vrs_context ctx, T **counters, size_t count) {
+    if (*counters) return VRS_OK;
+    VRS_HIP(ctx, hipMalloc(reinterpret_cast<void **>(counters), count * sizeof(T)));
+    VRS_HIP(ctx, hipMemsetAsync(*counters, 0, count * sizeof(T), ctx->stream));
+    return VRS_OK;
+}
+template <typename T>
+int read_counters(vrs_context ctx, const T *counters, T *out, size_t count) {
+    std::fill(out, out + count, T{});
+    if (!counters) return VRS_OK;
+    VRS_HIP(ctx, hipSetDevice(ctx->device));
+    if (const int rc = settle_pending(ctx)) return rc;
+    VRS_HIP(ctx, hipMemcpyAsync(out, counters, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    VRS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VRS_OK;
+}
 int sort_one_read(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values, vrs_buffer values_tmp,
                          uint32_t n, int key_bytes, uint32_t key_base);
 int sort_all_passes(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer values,

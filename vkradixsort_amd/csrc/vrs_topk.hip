@@ -22,16 +22,13 @@ namespace {
 
 __device__ __forceinline__ bool sel_less(uint32_t r, const TopkSel &s) { return s.shift < 32u && (r >> s.shift) < (s.prefix >> s.shift); }
 __device__ __forceinline__ bool sel_match(uint32_t r, const TopkSel &s) { return s.shift >= 32u || (r >> s.shift) == (s.prefix >> s.shift); }
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
 
 // counts digit d of the calling lane; one add for the whole instruction when every active lane has the same digit (equal keys)
 __device__ __forceinline__ void hist_add(uint32_t *s_hist, uint32_t d) {
     const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
     const uint64_t active = __ballot(1);
     if (__ballot(d == d0) == active) {
-        if (lanes_below(active) == 0u) atomicAdd(&s_hist[d0], static_cast<uint32_t>(__popcll(active)));
+        if (count_below(active) == 0u) atomicAdd(&s_hist[d0], static_cast<uint32_t>(__popcll(active)));
     } else {
         atomicAdd(&s_hist[d], 1u);
     }
@@ -168,10 +165,10 @@ __device__ __forceinline__ uint2 emit_tile(Load load, uint32_t cnt, uint32_t pos
         const uint64_t bl = __ballot(lt), be = __ballot(eq);
         uint32_t slot = 0xFFFFFFFFu;
         if (lt) {
-            slot = lt_base + s_scan[i * WAVES + wave] + lanes_below(bl);
+            slot = lt_base + s_scan[i * WAVES + wave] + count_below(bl);
             if (slot >= sel.lt) slot = 0xFFFFFFFFu;
         } else if (eq) {
-            const uint32_t er = eq_base + s_scan[E + i * WAVES + wave] + lanes_below(be);
+            const uint32_t er = eq_base + s_scan[E + i * WAVES + wave] + count_below(be);
             if (er < sel.need) slot = sel.lt + er;
         }
         if (slot < m) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 
+#include "vrs_key_order.hpp"
 #include "vrs_segmented.hpp"
 
 namespace vrs {
@@ -33,12 +34,12 @@ __host__ __device__ inline int topk_tier(uint32_t b, uint32_t e, uint32_t n, uin
 
 // r(x): ascending r is the order the selection takes the keys in (VRS_KEYS_FLOAT32_TO_SORTABLE for floats; ~ for the largest)
 __host__ __device__ inline uint32_t topk_rank(uint32_t x, int key_type, bool largest) {
-    uint32_t r = key_type == kTopkI32 ? x ^ 0x80000000u : key_type == kTopkF32 ? x ^ ((x & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u) : x;
+    const uint32_t r = key_type == kTopkI32 ? key_from_signed(x) : key_type == kTopkF32 ? key_from_float(x) : x;
     return largest ? ~r : r;
 }
 __host__ __device__ inline uint32_t topk_unrank(uint32_t r, int key_type, bool largest) {
     if (largest) r = ~r;
-    return key_type == kTopkI32 ? r ^ 0x80000000u : key_type == kTopkF32 ? r ^ ((r & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu) : r;
+    return key_type == kTopkI32 ? signed_from_key(r) : key_type == kTopkF32 ? float_from_key(r) : r;
 }
 
 // How far the selection of one segment has got: the selected set is every key whose top (32 - shift) bits of r are below prefix's, then

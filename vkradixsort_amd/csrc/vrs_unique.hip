@@ -9,15 +9,13 @@
 //   The grid-stride loops count in 64 bits: a 32-bit i + stride wraps to a small value still below a bound near 2^32 (a hang).
 #include "vrs_unique.hpp"
 
+#include "vrs_device.hpp"
+
 #include <algorithm>
 
 namespace vrs {
 namespace {
 
-__device__ __forceinline__ uint32_t rle_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t rle_below(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
@@ -72,7 +70,7 @@ template <typename K, bool FULL>
 __device__ __forceinline__ void rle_tile(const RleArgs &a, uint32_t tile, uint32_t *s_prefix, uint32_t *s_wave) {
     const K *keys = static_cast<const K *>(a.keys);
     auto *status = reinterpret_cast<unsigned long long *>(a.status + 16);
-    const uint32_t n = a.n, lane = rle_lane(), wave = threadIdx.x >> 6;
+    const uint32_t n = a.n, lane = lane_id(), wave = threadIdx.x >> 6;
     const uint32_t base = tile * kRleTile + wave * (kRleItems * 64u);  // first key of my wave (may lie beyond n in the last tile)
     // the tail tile: which of my items lie below n, as bits of one VGPR (not 16 exec masks live through the tile); its loads clamp
     uint32_t below = 0xFFFFu;
@@ -98,7 +96,7 @@ __device__ __forceinline__ void rle_tile(const RleArgs &a, uint32_t tile, uint32
         if (lane == 0u) prev = wrap;
         const bool head = valid(j) && (i == 0u || key[j] != prev);
         const uint64_t m = __ballot(head);
-        incl[j] = run + rle_below(m) + (head ? 1u : 0u);
+        incl[j] = run + count_below(m) + (head ? 1u : 0u);
         asm volatile("" : "+v"(incl[j]));  // computed here, kept in a VGPR: not 16 ballot masks kept alive in SGPRs until the stores
         run += static_cast<uint32_t>(__popcll(m));
         heads |= (head ? 1u : 0u) << j;

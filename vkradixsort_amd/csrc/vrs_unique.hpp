@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "vrs_key_order.hpp"
+
 namespace vrs {
 
 constexpr uint32_t kRleThreads = 256u;                    // 4 waves
@@ -24,18 +26,16 @@ __host__ __device__ inline int unique_key_bytes(int key_type) { return key_type 
 
 // r(x): ascending r is ascending x (two's complement for I*, the IEEE-754 total order for F*, VRS_KEYS_FLOAT32_TO_SORTABLE widened)
 __host__ __device__ inline uint32_t unique_rank(uint32_t x, int key_type) {
-    return key_type == kUniqueI32 ? x ^ 0x80000000u : key_type == kUniqueF32 ? x ^ ((x & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u) : x;
+    return key_type == kUniqueI32 ? key_from_signed(x) : key_type == kUniqueF32 ? key_from_float(x) : x;
 }
 __host__ __device__ inline uint32_t unique_unrank(uint32_t r, int key_type) {
-    return key_type == kUniqueI32 ? r ^ 0x80000000u : key_type == kUniqueF32 ? r ^ ((r & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu) : r;
+    return key_type == kUniqueI32 ? signed_from_key(r) : key_type == kUniqueF32 ? float_from_key(r) : r;
 }
 __host__ __device__ inline uint64_t unique_rank(uint64_t x, int key_type) {
-    constexpr uint64_t top = 1ull << 63;
-    return key_type == kUniqueI64 ? x ^ top : key_type == kUniqueF64 ? x ^ ((x & top) ? ~0ull : top) : x;
+    return key_type == kUniqueI64 ? key_from_signed(x) : key_type == kUniqueF64 ? key_from_float(x) : x;
 }
 __host__ __device__ inline uint64_t unique_unrank(uint64_t r, int key_type) {
-    constexpr uint64_t top = 1ull << 63;
-    return key_type == kUniqueI64 ? r ^ top : key_type == kUniqueF64 ? r ^ ((r & top) ? top : ~0ull) : r;
+    return key_type == kUniqueI64 ? signed_from_key(r) : key_type == kUniqueF64 ? float_from_key(r) : r;
 }
 
 inline size_t rle_up(size_t x) { return (x + 255u) & ~static_cast<size_t>(255u); }

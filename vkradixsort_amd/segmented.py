@@ -7,7 +7,8 @@ from __future__ import annotations
 
 import ctypes
 
-from . import capi, engine
+from . import capi
+from ._torch import buffers, context_for, positions_to_int64, row_offsets
 from .capi import VrsError
 
 
@@ -30,21 +31,6 @@ def segmented_stats(ctx) -> dict:
     c = [ctypes.c_uint64() for _ in range(4)]
     ctx.check(ctx.lib.vrs_segmented_stats(ctx.handle, *(ctypes.byref(v) for v in c)))
     return {"wave": c[0].value, "block": c[1].value, "global": c[2].value, "one_call": c[3].value}
-
-
-_contexts: dict = {}
-
-
-def _context_for(torch, device):
-    """One context per (device, torch stream), borrowing that stream."""
-    stream = torch.cuda.current_stream(device)
-    key = (device.index, stream.cuda_stream)
-    ctx = _contexts.get(key)
-    if ctx is None:
-        ctx = engine.GPUContext(device.index, stream=stream.cuda_stream)
-        ctx.init()
-        _contexts[key] = ctx
-    return ctx
 
 
 def sort_rows(x, return_indices: bool = False):
@@ -73,24 +59,14 @@ def sort_rows(x, return_indices: bool = False):
     idx = torch.arange(length, dtype=torch.int32, device=device).repeat(rows) if return_indices else None
     if n == 0:
         return (out, torch.zeros_like(out, dtype=torch.int64)) if return_indices else out
-    ctx = _context_for(torch, device)
-    bounds = torch.arange(rows + 1, dtype=torch.int64, device=device) * length
-    offsets = ((bounds + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)  # uint32 bit patterns
-    tensors = [out, torch.empty_like(out), offsets] + ([idx, torch.empty_like(idx)] if return_indices else [])
-    S = engine.Buffer.BufferSettings
-    bufs = [engine.Buffer(ctx, S(t.numel() * 4), device_ptr=t.data_ptr()) for t in tensors]
-    try:
-        lib = ctx.lib
-        ctx.check(lib.vrs_transform_keys(ctx.handle, bufs[0].handle, n, to_keys))
+    ctx = context_for(device)
+    idx_tmp = torch.empty_like(idx) if return_indices else None
+    with buffers(ctx, out, torch.empty_like(out), row_offsets(rows, length, device), idx, idx_tmp) as h:
+        keys, keys_tmp, offsets, vals, vals_tmp = h
+        ctx.check(ctx.lib.vrs_transform_keys(ctx.handle, keys, n, to_keys))
         if return_indices:
-            sort_segments(ctx, bufs[0], bufs[1], bufs[2], n, rows, values=bufs[3], values_tmp=bufs[4])
+            ctx.check(ctx.lib.vrs_sort_segments_pairs_u32(ctx.handle, keys, keys_tmp, vals, vals_tmp, n, offsets, rows))
         else:
-            sort_segments(ctx, bufs[0], bufs[1], bufs[2], n, rows)
-        ctx.check(lib.vrs_transform_keys(ctx.handle, bufs[0].handle, n, from_keys))
-    finally:
-        for b in bufs:
-            b.release()
-    if not return_indices:
-        return out
-    pos = idx.view(rows, length).long()  # uint32 positions: an int32 view of them goes negative from 2^31 on
-    return out, (pos & 0xFFFFFFFF if length > 1 << 31 else pos)
+            ctx.check(ctx.lib.vrs_sort_segments_u32(ctx.handle, keys, keys_tmp, n, offsets, rows))
+        ctx.check(ctx.lib.vrs_transform_keys(ctx.handle, keys, n, from_keys))
+    return (out, positions_to_int64(idx.view(rows, length), length)) if return_indices else out

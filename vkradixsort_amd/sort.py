@@ -6,9 +6,9 @@ writes the values back from the sorted ranks and the int64 indices from the posi
 """
 from __future__ import annotations
 
-from . import capi, engine
+from . import capi
+from ._torch import buffers, context_for, row_offsets
 from .capi import VrsError
-from .segmented import _context_for
 
 
 def _dtype_code(torch, dtype):
@@ -51,17 +51,10 @@ def _run(x, dim: int, descending: bool, want_values: bool, want_indices: bool):
     pos_tmp = torch.empty_like(pos)
     values = torch.empty(n if want_values else 0, dtype=x.dtype, device=device)
     indices = torch.empty(n if want_indices else 0, dtype=torch.int64, device=device)
-    tensors = [xt, ranks, ranks_tmp, pos, pos_tmp, values, indices]
-    if rows > 1 and L > 1:
-        bounds = torch.arange(rows + 1, dtype=torch.int64, device=device) * L
-        tensors.append(((bounds + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32))  # uint32 bit patterns
-    ctx = _context_for(torch, device)
-    S = engine.Buffer.BufferSettings
-    bufs = [engine.Buffer(ctx, S(t.numel() * t.element_size()), device_ptr=t.data_ptr()) if t.numel() else None for t in tensors]
-    h = [b.handle if b is not None else None for b in bufs]
-    src, rk, rk_tmp, ps, ps_tmp, vals, idx = h[:7]
+    offsets = row_offsets(rows, L, device) if rows > 1 and L > 1 else None
+    ctx = context_for(device)
     lib = ctx.lib
-    try:
+    with buffers(ctx, xt, ranks, ranks_tmp, pos, pos_tmp, values, indices, offsets) as (src, rk, rk_tmp, ps, ps_tmp, vals, idx, offs):
         ctx.check(lib.vrs_sort_rank_keys(ctx.handle, src, n, L, code, flags, rk, ps))
         if L > 1:
             w = "u64" if wide else "u32"
@@ -71,15 +64,10 @@ def _run(x, dim: int, descending: bool, want_values: bool, want_indices: bool):
                 else:
                     ctx.check(getattr(lib, f"vrs_sort_keys_{w}")(ctx.handle, rk, rk_tmp, n))
             elif with_pos:
-                ctx.check(getattr(lib, f"vrs_sort_segments_pairs_{w}")(ctx.handle, rk, rk_tmp, ps, ps_tmp, n, h[7], rows))
+                ctx.check(getattr(lib, f"vrs_sort_segments_pairs_{w}")(ctx.handle, rk, rk_tmp, ps, ps_tmp, n, offs, rows))
             else:
-                ctx.check(getattr(lib, f"vrs_sort_segments_{w}")(ctx.handle, rk, rk_tmp, n, h[7], rows))
-        ctx.check(lib.vrs_sort_restore(ctx.handle, src, rk, ps, n, L, code, flags, vals if want_values else None,
-                                       idx if want_indices else None))
-    finally:
-        for b in bufs:
-            if b is not None:
-                b.release()
+                ctx.check(getattr(lib, f"vrs_sort_segments_{w}")(ctx.handle, rk, rk_tmp, n, offs, rows))
+        ctx.check(lib.vrs_sort_restore(ctx.handle, src, rk, ps, n, L, code, flags, vals, idx))
     shape = xt.shape
     out_v = values.view(shape).movedim(-1, dim) if want_values else None
     out_i = indices.view(shape).movedim(-1, dim) if want_indices else None

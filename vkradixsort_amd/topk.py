@@ -7,22 +7,17 @@ from __future__ import annotations
 
 import ctypes
 
-from . import capi, engine
+from . import capi
+from ._torch import buffers, context_for, positions_to_int64, row_offsets
 from .capi import VrsError
-from .segmented import _context_for
 
 _KEY_TYPES = {"u32": capi.VRS_TOPK_U32, "i32": capi.VRS_TOPK_I32, "f32": capi.VRS_TOPK_F32}
 
 
 def scratch_bytes(num_elements: int, num_segments: int, k: int, largest: bool = False, sorted: bool = True) -> int:
     """Bytes of scratch vrs_topk_segments needs for this shape (no device)."""
-    out = ctypes.c_uint64()
-    lib = capi.load_library()
     flags = (capi.VRS_TOPK_LARGEST if largest else 0) | (capi.VRS_TOPK_SORTED if sorted else 0)
-    rc = lib.vrs_topk_scratch_bytes(num_elements, num_segments, k, flags, ctypes.byref(out))
-    if rc != capi.VRS_OK:
-        raise VrsError(rc, lib.vrs_last_error(None).decode())
-    return out.value
+    return capi.query_u64("vrs_topk_scratch_bytes", num_elements, num_segments, k, flags)
 
 
 def topk_segments(ctx, keys, offsets, num_elements: int, num_segments: int, k: int, out_keys, out_indices=None, scratch=None,
@@ -80,19 +75,9 @@ def topk(x, k: int, dim: int = -1, largest: bool = True, sorted: bool = True):
     idx = torch.empty(shape, dtype=torch.int32, device=device)
     if k == 0 or rows == 0:
         return values, idx.long()
-    ctx = _context_for(torch, device)
-    bounds = torch.arange(rows + 1, dtype=torch.int64, device=device) * length
-    offsets = ((bounds + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)  # uint32 bit patterns
+    ctx = context_for(device)
     flags = (capi.VRS_TOPK_LARGEST if largest else 0) | (capi.VRS_TOPK_SORTED if sorted else 0)
     scratch = torch.empty(max(scratch_bytes(n, rows, k, largest, sorted), 4), dtype=torch.uint8, device=device)
-    S = engine.Buffer.BufferSettings
-    tensors = [x, offsets, values, idx, scratch]
-    bufs = [engine.Buffer(ctx, S(max(t.numel() * t.element_size(), 4)), device_ptr=t.data_ptr()) for t in tensors]
-    try:
-        ctx.check(ctx.lib.vrs_topk_segments(ctx.handle, bufs[0].handle, n, bufs[1].handle, rows, k, key_type, flags, bufs[2].handle,
-                                            bufs[3].handle, bufs[4].handle))
-    finally:
-        for b in bufs:
-            b.release()
-    # the positions are uint32: an int32 view of them goes negative from 2^31 on
-    return values, (idx.long() & 0xFFFFFFFF if length > 1 << 31 else idx.long())
+    with buffers(ctx, x, row_offsets(rows, length, device), values, idx, scratch) as (keys, offsets, out_keys, out_idx, scr):
+        ctx.check(ctx.lib.vrs_topk_segments(ctx.handle, keys, n, offsets, rows, k, key_type, flags, out_keys, out_idx, scr))
+    return values, positions_to_int64(idx, length)

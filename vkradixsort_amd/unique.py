@@ -6,28 +6,17 @@ torch.unique_consecutive of an int32, int64, float32 or float64 tensor on a GPU,
 """
 from __future__ import annotations
 
-import ctypes
-
-from . import capi, engine
+from . import capi
+from ._torch import buffers, context_for, positions_to_int64
 from .capi import VrsError
-from .segmented import _context_for
 
 _KEY_TYPES = {"u32": capi.VRS_UNIQUE_U32, "i32": capi.VRS_UNIQUE_I32, "f32": capi.VRS_UNIQUE_F32,
               "u64": capi.VRS_UNIQUE_U64, "i64": capi.VRS_UNIQUE_I64, "f64": capi.VRS_UNIQUE_F64}
 
 
-def _scratch(fn, *args) -> int:
-    out = ctypes.c_uint64()
-    lib = capi.load_library()
-    rc = getattr(lib, fn)(*args, ctypes.byref(out))
-    if rc != capi.VRS_OK:
-        raise VrsError(rc, lib.vrs_last_error(None).decode())
-    return out.value
-
-
 def rle_scratch_bytes(num_elements: int, key_bytes: int = 4, counts: bool = False) -> int:
     """Bytes of scratch vrs_run_length_encode needs (no device); counts=True when out_counts is given without out_offsets."""
-    return _scratch("vrs_run_length_encode_scratch_bytes", num_elements, key_bytes, capi.VRS_RLE_COUNTS if counts else 0)
+    return capi.query_u64("vrs_run_length_encode_scratch_bytes", num_elements, key_bytes, capi.VRS_RLE_COUNTS if counts else 0)
 
 
 def unique_scratch_bytes(num_elements: int, key_type: str = "u32", inverse: bool = False, counts: bool = False) -> int:
@@ -35,7 +24,7 @@ def unique_scratch_bytes(num_elements: int, key_type: str = "u32", inverse: bool
     if key_type not in _KEY_TYPES:
         raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, f"key_type must be one of {sorted(_KEY_TYPES)}")
     flags = (capi.VRS_UNIQUE_INVERSE if inverse else 0) | (capi.VRS_UNIQUE_COUNTS if counts else 0)
-    return _scratch("vrs_unique_scratch_bytes", num_elements, _KEY_TYPES[key_type], flags)
+    return capi.query_u64("vrs_unique_scratch_bytes", num_elements, _KEY_TYPES[key_type], flags)
 
 
 def _h(b):
@@ -101,30 +90,15 @@ def _run(torch, x, return_inverse: bool, return_counts: bool, consecutive: bool,
     else:
         sb = unique_scratch_bytes(n, key_type, inverse=return_inverse, counts=return_counts)
     scratch = torch.empty(max(sb, 4), dtype=torch.uint8, device=device)
-    ctx = _context_for(torch, device)
-    S = engine.Buffer.BufferSettings
-    tensors = [flat, values, runs, scratch] + ([inverse] if return_inverse else []) + ([counts] if return_counts else [])
-    bufs = [engine.Buffer(ctx, S(max(t.numel() * t.element_size(), 4)), device_ptr=t.data_ptr()) for t in tensors]
-    inv_b = bufs[4] if return_inverse else None
-    cnt_b = bufs[-1] if return_counts else None
-    try:
+    ctx = context_for(device)
+    with buffers(ctx, flat, values, runs, scratch, inverse, counts) as (keys, out_keys, num_runs, scr, inv, cnt):
         if consecutive:
-            ctx.check(ctx.lib.vrs_run_length_encode(ctx.handle, bufs[0].handle, n, kb, bufs[1].handle, None, _h(cnt_b), _h(inv_b),
-                                                    bufs[2].handle, bufs[3].handle))
+            ctx.check(ctx.lib.vrs_run_length_encode(ctx.handle, keys, n, kb, out_keys, None, cnt, inv, num_runs, scr))
         else:
-            ctx.check(ctx.lib.vrs_unique(ctx.handle, bufs[0].handle, n, _KEY_TYPES[key_type], bufs[1].handle, _h(cnt_b), _h(inv_b),
-                                         bufs[2].handle, bufs[3].handle))
-    finally:
-        for b in bufs:
-            b.release()
+            ctx.check(ctx.lib.vrs_unique(ctx.handle, keys, n, _KEY_TYPES[key_type], out_keys, cnt, inv, num_runs, scr))
     R = int(runs.item())  # the one host synchronisation: the size of the result
-
-    def widen(t):  # uint32 bit patterns to int64 (an int32 view of them goes negative from 2^31 on)
-        w = t.long()
-        return w & 0xFFFFFFFF if n > 1 << 31 else w
-
-    inv = widen(inverse).view(x.shape) if return_inverse else None
-    return _result(values[:R], inv, widen(counts[:R]) if return_counts else None, return_inverse, return_counts)
+    inv = positions_to_int64(inverse, n).view(x.shape) if return_inverse else None
+    return _result(values[:R], inv, positions_to_int64(counts[:R], n) if return_counts else None, return_inverse, return_counts)
 
 
 def _empty(torch, x, return_inverse: bool, return_counts: bool):

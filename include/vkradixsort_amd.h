@@ -410,6 +410,60 @@ int vrs_topk_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, uint3
 int vrs_topk_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments);
 
 /*
+ * Sorted-sequence search (build extension; no reference counterpart): torch.searchsorted / torch.bucketize / numpy.searchsorted.
+ * `boundaries`: num_boundaries elements of `dtype` (a vrs_sort_dtype) as rows of boundary_row_len, each ascending in r; `queries`:
+ * num_queries elements of the same dtype as rows of query_row_len.  Either there is exactly one boundary row, which every query
+ * searches (bucketize, 1-D searchsorted), or as many as query rows, query row i searching boundary row i (N-D searchsorted).
+ * With r = the rank vrs_sort_rank_keys gives (unsigned as is; signed with the sign bit flipped; floats by value with -0.0 == +0.0 and
+ * every NaN, whatever its sign or payload, equal to every other NaN and above +inf):
+ *     out[q] = number of boundaries b of the query's row with r(b) <  r(queries[q])      (left, the default)
+ *     out[q] = number of boundaries b of the query's row with r(b) <= r(queries[q])      (VRS_SEARCH_RIGHT)
+ * as uint32 words (the bit patterns of int32 below 2^31), or int64 with VRS_SEARCH_OUT_INT64.  This is numpy.searchsorted's answer
+ * always and torch.searchsorted's whenever the boundaries hold no NaN (NaN queries included); with NaN boundaries torch's answer
+ * depends on the midpoints its binary search visits, this one does not.  Boundaries that are not ascending: some value in
+ * [0, boundary_row_len] per query, no fault.  sorter: NULL, or num_boundaries int64 positions within the row -- boundary j of a row is
+ * then row[sorter[j]] (an entry outside [0, boundary_row_len) reads the row's last element).  The rank map is applied as elements are
+ * read; boundaries, queries and sorter are never written, nor are bytes of `out` past num_queries entries.
+ * num_queries == 0: VRS_OK, nothing done.  num_boundaries == 0: every output 0.  A NULL context, queries or out (boundaries, when
+ * there are any), an unknown dtype or flag bit, element counts that are not whole rows, row counts that neither match nor equal one
+ * and undersized buffers: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Both element counts are below 2^32.
+ * Tiers (vrs_search_tier, decided by vrs_search_tier_for from the shape and three thresholds): a row whose ranks fit
+ * VRS_TUNE_SEARCH_LDS_BYTES is staged in LDS by every workgroup and searched there; 1- and 2-byte dtypes with one boundary row and
+ * VRS_TUNE_SEARCH_TABLE_MIN_QUERIES queries or more search every bit pattern once and then look every query up in that table;
+ * longer rows with VRS_TUNE_SEARCH_INDEX_MIN_QUERIES queries or more per row are searched through a sampled index (the rank of the
+ * last boundary of every 128-byte line, written by one pass per call; its top level in LDS): three or four dependent global line
+ * fetches per query instead of about log2(boundary_row_len) - 5; everything else is a plain lower / upper bound in global memory.
+ * scratch: at least the bytes vrs_search_plan (or vrs_search_scratch_bytes for the tier) reports, may be NULL when that is 0 (the LDS
+ * and direct tiers); contents on entry unspecified, afterwards unspecified.  Stream-ordered on the context's stream; the call only
+ * enqueues (after settling a pending one-call sort) and never waits for the device.
+ */
+enum { VRS_SEARCH_RIGHT = 1, VRS_SEARCH_OUT_INT64 = 2 }; /* flags */
+typedef enum vrs_search_tier {
+    VRS_SEARCH_LDS = 0,    /* the row's ranks fit VRS_TUNE_SEARCH_LDS_BYTES (no boundaries at all included) */
+    VRS_SEARCH_TABLE = 1,  /* 1- / 2-byte dtype, one boundary row, VRS_TUNE_SEARCH_TABLE_MIN_QUERIES queries or more (1-byte: 1/256 of it) */
+    VRS_SEARCH_DIRECT = 2, /* longer rows, fewer than VRS_TUNE_SEARCH_INDEX_MIN_QUERIES queries per boundary row */
+    VRS_SEARCH_INDEXED = 3 /* longer rows, that many queries or more */
+} vrs_search_tier;
+int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_boundaries, uint32_t boundary_row_len, vrs_buffer queries,
+                      uint32_t num_queries, uint32_t query_row_len, int dtype, int flags, vrs_buffer sorter /* may be NULL */,
+                      vrs_buffer out, vrs_buffer scratch /* may be NULL when no scratch is needed */);
+/* the classification both the device and the tests use: a pure function, needs no device.  The three thresholds are the values of
+ * VRS_TUNE_SEARCH_LDS_BYTES, _TABLE_MIN_QUERIES and _INDEX_MIN_QUERIES (0 = never that tier; rows without boundaries are always
+ * VRS_SEARCH_LDS).  Refuses what vrs_search_sorted refuses about the shape and the dtype.  *tier = VRS_SEARCH_*. */
+int vrs_search_tier_for(uint32_t num_boundaries, uint32_t boundary_row_len, uint32_t num_queries, uint32_t query_row_len, int dtype,
+                        uint32_t lds_bytes, uint32_t table_min_queries, uint32_t index_min_queries, int *tier);
+/* the scratch a call in `tier` needs: a pure function, needs no device.  0 for VRS_SEARCH_LDS and VRS_SEARCH_DIRECT; the table: 4 bytes
+ * per bit pattern (1 KiB / 256 KiB); the index: with e = the dtype's bytes and w = its rank's bytes (vrs_sort_rank_bytes), at most
+ * (num_boundaries * e / 128) * w * 33 / 32 + (has_sorter ? num_boundaries * w : 0) + 1024 bytes. */
+int vrs_search_scratch_bytes(uint32_t num_boundaries, uint32_t boundary_row_len, int dtype, int has_sorter, int tier, uint64_t *bytes);
+/* the tier vrs_search_sorted will take on this context (its tuning as it stands) and the scratch that needs; no device work */
+int vrs_search_plan(vrs_context ctx, uint32_t num_boundaries, uint32_t boundary_row_len, uint32_t num_queries, uint32_t query_row_len,
+                    int dtype, int has_sorter, int *tier, uint64_t *scratch_bytes);
+/* cumulative per context: calls each tier ran (calls without queries or without boundaries run none).  Counted on the host: does not
+ * wait for the stream.  Any pointer may be NULL. */
+int vrs_search_stats(vrs_context ctx, uint64_t *lds_calls, uint64_t *table_calls, uint64_t *direct_calls, uint64_t *indexed_calls);
+
+/*
  * Run-length encoding (build extension; no reference counterpart -- the reference's callers find each cell's or tile's [start, end)
  * in the sorted ids themselves): n keys of key_bytes (4 or 8) each, in any order, as maximal runs of bit-identical consecutive keys
  * (torch.unique_consecutive).  With R runs: out_keys[j] = the key of run j, out_offsets[j] = its first position and out_offsets[R] = n,
@@ -781,6 +835,14 @@ typedef enum vrs_tuning_key {
     VRS_TUNE_TOPK_GRID_MIN_KEYS = 28, /* top-k: segments of this many keys or more take the grid tier (every phase one launch over all of
                                        them); shorter ones beyond the LDS tier are streamed by one workgroup each.  0 = never.  Default 2^17 (the measured
                                        crossover, DESIGN "K7") */
+    VRS_TUNE_SEARCH_LDS_BYTES = 29, /* sorted-sequence search: a boundary row whose ranks (4 bytes each, 8 for int64 / float64) take up to this many
+                                       bytes is staged and searched in LDS; also the room of the indexed tier's top level.  0 .. 163840.  Default
+                                       65536 (DESIGN "K10") */
+    VRS_TUNE_SEARCH_TABLE_MIN_QUERIES = 30, /* sorted-sequence search, 2-byte dtypes with one boundary row: from this many queries on every bit
+                                       pattern is searched once and the queries are table lookups; 1-byte dtypes from 1/256 of it (at least 1).
+                                       0 = never.  Default 65536 */
+    VRS_TUNE_SEARCH_INDEX_MIN_QUERIES = 31, /* sorted-sequence search, rows beyond the LDS tier: from this many queries per boundary row on the call
+                                       builds the sampled index first.  0 = never (plain lower / upper bound).  Default 65536 */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

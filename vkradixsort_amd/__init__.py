@@ -6,12 +6,14 @@ engine   the same interface for Python callers (tests, bench.py), a thin ctypes 
 segmented  many independent segments sorted in one call (sort_segments over Buffers, sort_rows for 2-D torch tensors)
 topk       the k smallest / largest keys of every segment by radix select (topk_segments over Buffers, topk for torch tensors)
 sort       torch.sort / torch.argsort drop-ins: any dim, descending, nine dtypes, torch's order bit for bit (sort, sort_values, argsort)
+search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
            for torch tensors)
 """
 from .capi import PushConstants, VrsError, load_library  # noqa: F401
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
+from .search import bucketize, search_stats, searchsorted  # noqa: F401
 from .segmented import segmented_stats, sort_rows, sort_segments  # noqa: F401
 from .sort import argsort, sort, sort_values  # noqa: F401
 from .topk import topk, topk_segments, topk_stats  # noqa: F401

@@ -96,6 +96,13 @@ RLE_TILE = 4096
 (VRS_SORT_INT8, VRS_SORT_UINT8, VRS_SORT_INT16, VRS_SORT_INT32, VRS_SORT_INT64, VRS_SORT_FLOAT16, VRS_SORT_BFLOAT16, VRS_SORT_FLOAT32,
  VRS_SORT_FLOAT64) = range(9)
 VRS_SORT_DESCENDING = 1
+# sorted-sequence search (vrs_search_sorted): flags, tiers (vrs_search_tier), tuning keys and the library's defaults for them
+VRS_SEARCH_RIGHT, VRS_SEARCH_OUT_INT64 = 1, 2
+VRS_SEARCH_LDS, VRS_SEARCH_TABLE, VRS_SEARCH_DIRECT, VRS_SEARCH_INDEXED = 0, 1, 2, 3
+VRS_TUNE_SEARCH_LDS_BYTES, VRS_TUNE_SEARCH_TABLE_MIN_QUERIES, VRS_TUNE_SEARCH_INDEX_MIN_QUERIES = 29, 30, 31
+SEARCH_LDS_BYTES_DEFAULT, SEARCH_LDS_BYTES_MAX = 64 * 1024, 160 * 1024
+SEARCH_TABLE_MIN_QUERIES_DEFAULT, SEARCH_INDEX_MIN_QUERIES_DEFAULT = 1 << 16, 1 << 16
+SEARCH_LINE_BYTES = 128  # boundaries one index entry stands for
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -233,6 +240,11 @@ _SIGNATURES = [
     ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
     ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
     ("vrs_topk_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_search_sorted", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vrs_search_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
+    ("vrs_search_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, c_int, c_int, POINTER(c_uint64)]),
+    ("vrs_search_plan", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
+    ("vrs_search_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
     ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -171,6 +171,11 @@ struct vrs_context_t {
     // top-k selection (vrs_capi_topk.hip)
     vrs_topk_state *topk = nullptr;
     uint32_t topk_grid_min_keys = 1u << 17;  // VRS_TUNE_TOPK_GRID_MIN_KEYS (vrs::kTopkDefaultGridMinKeys)
+    // sorted-sequence search (vrs_capi_search.hip); the defaults are vrs_search.hpp's kSearchDefault*
+    uint32_t search_lds_bytes = 64u * 1024u;      // VRS_TUNE_SEARCH_LDS_BYTES
+    uint32_t search_table_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_TABLE_MIN_QUERIES
+    uint32_t search_index_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_INDEX_MIN_QUERIES
+    uint64_t search_calls[4] = {};                // calls per tier (vrs_search_stats)
 };
 
 struct vrs_buffer_t {

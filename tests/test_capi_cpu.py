@@ -376,3 +376,21 @@ def test_no_source_file_of_the_library_outgrows_its_seams():
     sizes = {p.name: sum(1 for _ in p.open()) for p in csrc.iterdir() if p.suffix in (".hip", ".hpp", ".h")}
     assert max(sizes.values()) <= 1200, sizes
     assert {"vrs_capi.hip", "vrs_capi_contract.hip", "vrs_capi_sort.hip", "vrs_capi_pool.hip", "vrs_capi_msd.hip", "vrs_host.hpp", "vrs_sort_form.hpp"} <= set(sizes)
+
+
+def test_one_call_launchers_take_named_argument_structs():
+    """the launch wrappers of the one-call sort, its hybrid and its pool form once took 8 to 21 positional parameters, nearly all of them
+    uint32_t / int / bool / pointers, so that two swapped arguments compiled; each takes (stream, one struct of named fields, events) now,
+    and stays so"""
+    import re
+    from pathlib import Path
+    header = (Path(capi.__file__).resolve().parent / "csrc" / "vrs_kernels.h").read_text()
+    launchers = ("launch_onesweep_scatter", "launch_msd_plan", "launch_pool_pass_b", "launch_msd_pass_b", "launch_pool_pass_a", "launch_pool_local_sort",
+                 "launch_pool_plan", "launch_digit_tables", "launch_digit_tables_msd", "launch_plan", "launch_pool_sample", "launch_msd_count_u64",
+                 "launch_msd_local_sort", "launch_msd_local_sort_u64")
+    for name in launchers:
+        declared = re.findall(r"hipError_t\s+%s\s*\(([^;]*)\)\s*;" % name, header)
+        assert len(declared) == 1, (name, declared)
+        params = [p.strip() for p in declared[0].split(",")]
+        assert len(params) <= 4, (name, params)  # (today: stream, args and, where the launch can be timed, events)
+        assert params[0] == "hipStream_t stream" and re.fullmatch(r"const \w+Args &\w+", params[1]), (name, params)

@@ -87,10 +87,52 @@ int main(int argc, char **argv) {
     uint32_t stamp = 0;
     printf("n=%u groups=%u tile_cap=%u tiles0=%u\n", n, G, tile_cap, tiles0);
 
+    vrs::LaunchSetup setup{};
+    setup.atomic_rank = true;
+    setup.xcc_map = xcc_map;
+    setup.spin_budget = 4096;
+    setup.compute_units = cus;
+    // one look-back pass of bare uint32 keys
+    auto scatter_pass = [&](uint32_t *in, uint32_t *out, uint32_t pass, uint32_t grid_tiles, vrs::LaunchEvents ev) {
+        vrs::OnesweepScatterArgs a{};
+        a.keys_in = in;
+        a.keys_out = out;
+        a.plan = plan;
+        a.pass = pass;
+        a.shift = 8 * pass;
+        a.status = status;
+        a.grid_tiles = grid_tiles;
+        a.forced = vrs::kForcedNo;
+        a.key_bytes = 4;
+        a.setup = setup;
+        return vrs::launch_onesweep_scatter(st, a, ev);
+    };
     auto one_sort = [&](bool marks_pass, int which) {
         CK(hipMemcpyAsync(d_a, d_src, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-        CK(vrs::launch_digit_tables(st, d_a, n, 4, 0, group_len, G, tables, status, rows * 256, cus, e_dt.le()));
-        CK(vrs::launch_plan(st, tables, plan, host_dev, ++stamp, n, group_len, G, T, tile_cap, tile_cap, cuts0));
+        vrs::DigitTablesArgs dt{};
+        dt.keys = d_a;
+        dt.key_bytes = 4;
+        dt.base_shift = 0;
+        dt.groups = G;
+        dt.tables = tables;
+        dt.status = status;
+        dt.status_words = rows * 256;
+        dt.setup = setup;
+        dt.geo.n = n;
+        dt.geo.group_len = group_len;
+        dt.geo.tile = T;
+        dt.geo.tile_cap = tile_cap;
+        dt.geo.blind_cap = tile_cap;
+        dt.geo.cuts0 = cuts0;
+        dt.geo.stamp = ++stamp;
+        dt.geo.host_head = host_dev;
+        CK(vrs::launch_digit_tables(st, dt, e_dt.le()));
+        vrs::PlanArgs pa{};
+        pa.tables = tables;
+        pa.plan = plan;
+        pa.groups = G;
+        pa.geo = dt.geo;
+        CK(vrs::launch_plan(st, pa));
         uint32_t *in = d_a, *out = d_b;
         for (uint32_t i = 0; i < 4; ++i) {
             if (marks_pass) {
@@ -98,7 +140,7 @@ int main(int argc, char **argv) {
                 CK(hipStreamSynchronize(st));
                 CK(hipMemcpyToSymbol(HIP_SYMBOL(g_marks), &m, sizeof(m)));
             }
-            CK(vrs::launch_onesweep_scatter(st, in, out, nullptr, nullptr, plan, i, 8 * i, status, i == 0 ? tiles0 : tile_cap, false, true, xcc_map, 4, 4096, -1, e_p[i].le()));
+            CK(scatter_pass(in, out, i, i == 0 ? tiles0 : tile_cap, e_p[i].le()));
             std::swap(in, out);
         }
         CK(hipStreamSynchronize(st));
@@ -193,7 +235,7 @@ int main(int argc, char **argv) {
         // after one_sort the status rows hold pass 3's tags; re-run pass 3 (input = buffer b after three swaps, output = a)
         Ev ev[4];
         for (int i = 0; i < 4; ++i)
-            CK(vrs::launch_onesweep_scatter(st, d_b, d_a, nullptr, nullptr, plan, 3, 24, status, tile_cap, false, true, xcc_map, 4, 4096, -1, ev[i].le()));
+            CK(scatter_pass(d_b, d_a, 3, tile_cap, ev[i].le()));
         CK(hipStreamSynchronize(st));
         printf("D look-back pass 3 re-run four times over published rows (no waits): %.1f %.1f %.1f %.1f us (in the sort: %.1f)\n", ev[0].us(), ev[1].us(), ev[2].us(), ev[3].us(), e_p[3].us());
     }

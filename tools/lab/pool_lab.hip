@@ -94,28 +94,71 @@ int main(int argc, char **argv) {
         hipLaunchKernelGGL(check_sorted, dim3(2048), dim3(256), 0, st, in, n, chk + 2);  // chk[3] = key sum of the input
         CK(hipMemsetAsync(reinterpret_cast<char *>(msd) + offsetof(vrs::MsdPlan, cursor_a), 0, vrs::kMsdCursorBytes, st));
         CK(hipEventRecord(ev[0], st));
-        const uint32_t par = r & 1u;
-        CK(vrs::launch_pool_sample(st, in, n, 0, ps, pool, room, par));  // (sample + layout kernels)
+        vrs::PoolForm form{};
+        form.n = n;
+        form.key_base = 0;
+        form.ps = ps;
+        form.pool = pool;
+        form.msd = msd;
+        form.par = r & 1u;
+        form.setup.xcc_map = xcc_map;
+        vrs::PoolSampleArgs sa{};
+        sa.form = form;
+        sa.keys = in;
+        sa.overflow_capacity = room;
+        CK(vrs::launch_pool_sample(st, sa));  // (sample + layout kernels)
         CK(hipEventRecord(ev[1], st));
-        CK(vrs::launch_pool_pass_a(st, in, partner, ovf, n, 0, ps, pool, msd, xcc_map, false, room, par));
+        vrs::PoolPassAArgs pa{};
+        pa.form = form;
+        pa.keys_in = in;
+        pa.keys_out = partner;
+        pa.overflow = ovf;
+        pa.overflow_capacity = room;
+        pa.misplace = false;
+        CK(vrs::launch_pool_pass_a(st, pa));
         CK(hipEventRecord(ev[2], st));
-        CK(vrs::launch_pool_plan(st, msd, pool, n, tiles_b, slack_cap, partner, ovf, 0, ps, shape.sub_bits, par));
+        vrs::PoolPlanArgs pl{};
+        pl.form = form;
+        pl.tiles_b_cap = tiles_b;
+        pl.slack_capacity = slack_cap;
+        pl.regions = partner;
+        pl.overflow = ovf;
+        pl.sub_bits = shape.sub_bits;
+        CK(vrs::launch_pool_plan(st, pl));
         CK(hipEventRecord(ev[3], st));
-        CK(vrs::launch_pool_pass_b(st, partner, ovf, slack, n, msd, pool, tiles_b, 0, vrs::pool_local_capacity(shape.local), slack_cap, xcc_map, 1000u + r, shape.sub_bits, par));
+        vrs::PoolPassBArgs pb{};
+        pb.form = form;
+        pb.regions = partner;
+        pb.overflow = ovf;
+        pb.slack = slack;
+        pb.tiles_b = tiles_b;
+        pb.local_cap = vrs::pool_local_capacity(shape.local);
+        pb.slack_capacity = slack_cap;
+        pb.stamp = 1000u + r;
+        pb.sub_bits = shape.sub_bits;
+        CK(vrs::launch_pool_pass_b(st, pb));
+        vrs::PoolLocalSortArgs ls{};
+        ls.form = form;
+        ls.slack = slack;
+        ls.keys_out = in;
+        ls.shape = shape;
+        ls.dev_head = head;
+        ls.host_head = nullptr;
+        ls.stamp = 1;
         CK(hipEventRecord(ev[4], st));
         if (getenv("POOL_LAB_ISOLATE")) {  // the local sort on a QUIET chip: whatever the second pass left dirty in the caches has been written back
             CK(hipStreamSynchronize(st));
             usleep(3000);
         }
         CK(hipEventRecord(ev[5], st));
-        CK(vrs::launch_pool_local_sort(st, slack, in, n, msd, pool, shape, head, nullptr, 1, par));
+        CK(vrs::launch_pool_local_sort(st, ls));
         CK(hipEventRecord(ev[6], st));
         float again_us = 0;
         if (getenv("POOL_LAB_ISOLATE")) {  // ... and once more (the same buckets from the same regions to the same places), behind another quiet period
             CK(hipStreamSynchronize(st));
             usleep(3000);
             CK(hipEventRecord(ev[8], st));
-            CK(vrs::launch_pool_local_sort(st, slack, in, n, msd, pool, shape, head, nullptr, 1, par));
+            CK(vrs::launch_pool_local_sort(st, ls));
             CK(hipEventRecord(ev[9], st));
             CK(hipStreamSynchronize(st));
             CK(hipEventElapsedTime(&again_us, ev[8], ev[9]));

@@ -51,28 +51,52 @@ int vrs_msd_partition_signal_u32(vrs_context ctx, vrs_buffer keys, vrs_buffer ou
     ctx->sub_cache.valid = false;
     // the counting read below clears the status words if anything has written them since they were last clear; the first MSD
     // pass then leaves them alone when it reserves, and writes them when it looks back
-    const size_t partition_zero_words = ctx->os_status_clean ? 0 : ctx->os_status_rows * VRS_RADIX_SORT_BINS;
+    const size_t partition_zero_words = status_words_to_zero(ctx);
     ctx->os_status_clean = reserves(ctx, n, false);
     vrs::LaunchEvents ev;
     if ((rc = profile_events(ctx, VRS_KERNEL_DIGIT_TABLES, &ev))) return rc;
-    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
+    const uint32_t stamp = next_stamp(ctx);
+    const vrs::LaunchSetup setup = launch_setup(ctx);
     // counting read: only the bucket histogram and the slices' top-byte counts (a key range below 27 bits gets the LSD
     // tables instead -- the plan kernel clears them again -- and leaves the histogram empty: the caller sees the shift)
-    VRS_HIP(ctx, vrs::launch_digit_tables_msd(ctx->stream, keys->ptr, n, g.group_len, ctx->os_tables, ctx->os_status,
-                                              partition_zero_words, ctx->scatter.compute_units, ctx->os_msd_counts, true, ev));
+    vrs::DigitTablesMsdArgs c{};
+    c.keys = keys->ptr;
+    c.n = n;
+    c.group_len = g.group_len;
+    c.tables = ctx->os_tables;
+    c.status = ctx->os_status;
+    c.status_words = partition_zero_words;
+    c.setup = setup;
+    c.msd_counts = ctx->os_msd_counts;
+    c.msd_only = true;
+    VRS_HIP(ctx, vrs::launch_digit_tables_msd(ctx->stream, c, ev));
     VRS_HIP(ctx, hipMemcpyAsync(counts_out->ptr, ctx->os_msd_counts, VRS_MSD_COUNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     // the counts are all a caller needs to start talking to its peers: the first pass below runs meanwhile
     if (counts_ready_event) VRS_HIP(ctx, hipEventRecord(static_cast<hipEvent_t>(counts_ready_event), ctx->stream));
-    VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, ctx->os_msd_counts, ctx->os_msd_plan, ctx->os_plan_a, ctx->os_plan,
-                                      ctx->os_host_head_dev, ctx->os_stamp, n, g.T, g.tiles_b_cap, g.local_cap, ctx->os_tables,
-                                      g.group_len, g.tile_cap, g.blind_cap, g.cuts0, 1u, 18u));
+    vrs::MsdPlanArgs p = msd_plan_args(ctx, g, n, stamp);
+    p.msd_only = vrs::kMsdOnlyFastCount;
+    p.max_shift = 18;
+    VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, p));
     // the first MSD pass, whatever the plan thinks of this shard's buckets (forced: the streams, not their armed copies) -- but not
-    // without counts (2: a key range below 27 bits, or a key outside the probed range: the workgroups leave at once, `out` is not
-    // written, and the caller, who sees the shift and the flag in counts_out, takes another shape)
+    // without counts (kForcedIfCounted: a key range below 27 bits, or a key outside the probed range: the workgroups leave at once,
+    // `out` is not written, and the caller, who sees the shift and the flag in counts_out, takes another shape)
     if ((rc = profile_events(ctx, VRS_KERNEL_LOOKBACK_SCATTER, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, keys->ptr, out->ptr, nullptr, nullptr, ctx->os_plan_a, 0, vrs::kShiftFromPlan,
-                                              ctx->os_status, g.tiles0, 2, ctx->scatter.atomic_rank, ctx->xcc_map, 4,
-                                              ctx->os_spin_budget, -1, ev, false, 0u, reserves(ctx, n, false) ? ctx->os_msd_plan : nullptr, drift_word(ctx)));
+    vrs::OnesweepScatterArgs a{};
+    a.keys_in = keys->ptr;
+    a.keys_out = out->ptr;
+    a.values_in = nullptr;
+    a.values_out = nullptr;
+    a.plan = ctx->os_plan_a;
+    a.pass = 0;
+    a.shift = vrs::kShiftFromPlan;
+    a.status = ctx->os_status;
+    a.grid_tiles = g.tiles0;
+    a.forced = vrs::kForcedIfCounted;
+    a.key_bytes = 4;
+    a.setup = setup;
+    // (the context's test hooks os_hold_tile / os_misplace do not apply to a partition: hold_tile, misplace and key_base keep their defaults)
+    a.reserve = reserves(ctx, n, false) ? ctx->os_msd_plan : nullptr;
+    VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, a, ev));
     return VRS_OK;
 }
 
@@ -92,18 +116,17 @@ int vrs_msd_finish_u32(vrs_context ctx, vrs_buffer grouped, vrs_buffer out, vrs_
     if ((rc = msd_half_setup(ctx, n, &st, &g, bucket_hint))) return rc;
     if ((rc = reservation_begin(ctx))) return rc;
     ctx->sub_cache.valid = false;
-    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
-    ctx->os_msd_half_stamp = ctx->os_stamp;
+    ctx->os_msd_half_stamp = next_stamp(ctx);
     // the look-back rows of the second pass must read "never written": the counting read of a whole sort clears them, here
     // nothing else does -- unless the last kernel that touched them was a local sort that cleared them (the previous round's)
-    if (!ctx->os_status_clean)
-        VRS_HIP(ctx, hipMemsetAsync(ctx->os_status, 0, ctx->os_status_rows * VRS_RADIX_SORT_BINS * sizeof(uint32_t), ctx->stream));
+    if (!ctx->os_status_clean) VRS_HIP(ctx, hipMemsetAsync(ctx->os_status, 0, status_words(ctx) * sizeof(uint32_t), ctx->stream));
     ctx->os_status_clean = false;
-    // the plan reads the caller's table in place (and leaves its histogram zeroed, like the context's own)
-    VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, static_cast<uint32_t *>(counts->ptr), ctx->os_msd_plan, ctx->os_plan_a, ctx->os_plan,
-                                      ctx->os_host_head_dev, ctx->os_stamp, n, g.T, g.tiles_b_cap, g.local_cap, ctx->os_tables,
-                                      g.group_len, g.tile_cap, g.blind_cap, g.cuts0, 1u, 18u,
-                                      reinterpret_cast<uint32_t *>(ctx->os_host_head_dev + 1)));
+    vrs::MsdPlanArgs p = msd_plan_args(ctx, g, n, ctx->os_msd_half_stamp);
+    p.msd_counts = static_cast<uint32_t *>(counts->ptr);  // the plan reads the caller's table in place (and leaves its histogram zeroed, like the context's own)
+    p.msd_only = vrs::kMsdOnlyFastCount;
+    p.max_shift = 18;
+    p.host_log = finish_log(ctx);
+    VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, p));
     st.kptr[0] = out->ptr;      // "home": the second pass writes here, the local sort works here
     st.kptr[1] = grouped->ptr;  // the partner holds the first pass's output
     st.cur_at_start = 0;
@@ -136,19 +159,29 @@ int vrs_msd_finish_grouped_u32(vrs_context ctx, vrs_buffer grouped, vrs_buffer o
     st.key_base = key_base;
     st.sub_bits = sub_bits;
     ctx->sub_cache.valid = false;
-    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
-    ctx->os_msd_half_stamp = ctx->os_stamp;
-    // the counting read clears the look-back rows unless the last kernel that touched them left them clear
-    const size_t zero_words = ctx->os_status_clean ? 0 : ctx->os_status_rows * VRS_RADIX_SORT_BINS;
-    ctx->os_status_clean = false;
+    ctx->os_msd_half_stamp = next_stamp(ctx);
     vrs::LaunchEvents ev;
+    vrs::DigitTablesMsdArgs c{};
+    c.keys = grouped->ptr;
+    c.n = n;
+    c.group_len = g.group_len;
+    c.tables = ctx->os_tables;
+    c.status = ctx->os_status;
+    c.status_words = status_words_to_zero(ctx);  // the counting read clears the look-back rows unless the last kernel that touched them left them clear
+    ctx->os_status_clean = false;
     if ((rc = profile_events(ctx, VRS_KERNEL_DIGIT_TABLES, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_digit_tables_msd(ctx->stream, grouped->ptr, n, g.group_len, ctx->os_tables, ctx->os_status, zero_words,
-                                              ctx->scatter.compute_units, ctx->os_msd_counts, true, ev, key_base, shift));
-    VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, ctx->os_msd_counts, ctx->os_msd_plan, ctx->os_plan_a, ctx->os_plan,
-                                      ctx->os_host_head_dev, ctx->os_stamp, n, g.T, g.tiles_b_cap, g.local_cap, ctx->os_tables,
-                                      g.group_len, g.tile_cap, g.blind_cap, g.cuts0, 1u, 18u,
-                                      reinterpret_cast<uint32_t *>(ctx->os_host_head_dev + 1), sub_bits));
+    c.setup = launch_setup(ctx);
+    c.msd_counts = ctx->os_msd_counts;
+    c.msd_only = true;
+    c.key_base = key_base;
+    c.force_shift = shift;
+    VRS_HIP(ctx, vrs::launch_digit_tables_msd(ctx->stream, c, ev));
+    vrs::MsdPlanArgs p = msd_plan_args(ctx, g, n, ctx->os_msd_half_stamp);
+    p.msd_only = vrs::kMsdOnlyFastCount;
+    p.max_shift = 18;
+    p.host_log = finish_log(ctx);
+    p.sub_bits = sub_bits;
+    VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, p));
     st.kptr[0] = out->ptr;
     st.kptr[1] = grouped->ptr;
     st.cur_at_start = 0;
@@ -257,23 +290,53 @@ int vrs_msd_finish_grouped_split_u32(vrs_context ctx, vrs_buffer grouped, vrs_bu
     const uint32_t slack = vrs::pool_slack_capacity(n, shape.sub_bits, top_bytes);
     if ((rc = pool_scratch(ctx, std::max(ctx->os_pool_overflow_cap, 32u), slack))) return rc == kPoolNoMemory ? counted() : rc;  // (no room for the slack buffer: the counted finish needs none)
     ctx->sub_cache.valid = false;
-    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
-    ctx->os_msd_half_stamp = ctx->os_stamp;
+    ctx->os_msd_half_stamp = next_stamp(ctx);
     ctx->os_pool_layout_valid = false;  // (the plan of grouped keys rewrites words a kept layout rests on: PoolPlan::shift)
-    const uint32_t par = (++ctx->os_pool_epoch) & 1u;
-    const uint32_t key_base = first_top_byte << 24;
+    vrs::PoolForm form{};  // (top_bits and pv keep their defaults: the cut of a whole sort, bare keys)
+    form.n = n;
+    form.key_base = first_top_byte << 24;
+    form.ps = vrs::pool_streams(n);
+    form.pool = ctx->os_pool_plan;
+    form.msd = ctx->os_msd_plan;
+    form.par = (++ctx->os_pool_epoch) & 1u;
+    form.setup = launch_setup(ctx);
     const uint32_t *keys_in = static_cast<const uint32_t *>(grouped->ptr);
     const uint32_t *keys_own = own ? static_cast<const uint32_t *>(own->ptr) : keys_in;  // (virtual slots from n on)
     vrs::LaunchEvents ev;
-    VRS_HIP(ctx, vrs::launch_pool_plan(ctx->stream, ctx->os_msd_plan, ctx->os_pool_plan, n, tiles_b, ctx->os_pool_slack_cap, keys_in, keys_own, key_base,
-                                       vrs::pool_streams(n), shape.sub_bits, par, &groups));
+    vrs::PoolPlanArgs pl{};
+    pl.form = form;
+    pl.tiles_b_cap = tiles_b;
+    pl.slack_capacity = ctx->os_pool_slack_cap;
+    pl.regions = keys_in;
+    pl.overflow = keys_own;
+    pl.sub_bits = shape.sub_bits;
+    pl.groups = &groups;
+    VRS_HIP(ctx, vrs::launch_pool_plan(ctx->stream, pl));
     if ((rc = profile_events(ctx, VRS_KERNEL_POOL_PASS_B, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_pool_pass_b(ctx->stream, keys_in, keys_own, ctx->os_pool_slack, n, ctx->os_msd_plan, ctx->os_pool_plan, tiles_b, key_base,
-                                         vrs::pool_local_capacity(shape.local), ctx->os_pool_slack_cap, ctx->xcc_map, ctx->os_stamp, shape.sub_bits, par, ev, true));
+    vrs::PoolPassBArgs pb{};
+    pb.form = form;
+    pb.regions = keys_in;
+    pb.overflow = keys_own;
+    pb.slack = ctx->os_pool_slack;
+    pb.tiles_b = tiles_b;
+    pb.local_cap = vrs::pool_local_capacity(shape.local);
+    pb.slack_capacity = ctx->os_pool_slack_cap;
+    pb.stamp = ctx->os_msd_half_stamp;
+    pb.sub_bits = shape.sub_bits;
+    pb.grouped = true;
+    VRS_HIP(ctx, vrs::launch_pool_pass_b(ctx->stream, pb, ev));
     if ((rc = profile_events(ctx, VRS_KERNEL_LOCAL_SORT, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_pool_local_sort(ctx->stream, ctx->os_pool_slack, static_cast<uint32_t *>(out->ptr), n, ctx->os_msd_plan, ctx->os_pool_plan, shape,
-                                             &ctx->os_plan->head, ctx->os_host_head_dev, ctx->os_stamp, par, ev, top_bytes,
-                                             reinterpret_cast<uint32_t *>(ctx->os_host_head_dev + 1)));
+    vrs::PoolLocalSortArgs ls{};
+    ls.form = form;
+    ls.slack = ctx->os_pool_slack;
+    ls.keys_out = static_cast<uint32_t *>(out->ptr);
+    ls.shape = shape;
+    ls.dev_head = &ctx->os_plan->head;
+    ls.host_head = ctx->os_host_head_dev;
+    ls.stamp = ctx->os_msd_half_stamp;
+    ls.top_bytes = top_bytes;
+    ls.host_log = finish_log(ctx);
+    VRS_HIP(ctx, vrs::launch_pool_local_sort(ctx->stream, ls, ev));
     return VRS_OK;
 }
 

@@ -94,37 +94,41 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     // first pass starts (the local sort of a taken sort leaves them so) and are written from here on
     vrs::PoolPayloads pv{};
     if (pairs) {
-        if (!ctx->os_status_clean)
-            VRS_HIP(ctx, hipMemsetAsync(ctx->os_status, 0, ctx->os_status_rows * VRS_RADIX_SORT_BINS * sizeof(uint32_t), ctx->stream));
+        if (!ctx->os_status_clean) VRS_HIP(ctx, hipMemsetAsync(ctx->os_status, 0, status_words(ctx) * sizeof(uint32_t), ctx->stream));
         ctx->os_status_clean = false;
         pv.values_home = static_cast<uint32_t *>(st.vptr[st.cur]);
         pv.values_partner = static_cast<uint32_t *>(st.vptr[st.cur ^ 1u]);
         pv.overflow_values = ctx->os_pool_overflow_vals;
         pv.slack_values = ctx->os_pool_slack_vals;
         pv.status = ctx->os_status;
-        pv.status_words = ctx->os_status_rows * VRS_RADIX_SORT_BINS;
+        pv.status_words = status_words(ctx);
         pv.spin_budget = ctx->os_spin_budget;
         pv.hold_tile = ctx->os_hold_tile;
         pv.top_bits = top_bits;
         pv.packed = ctx->os_pool_pairs_packed;
     }
-    const vrs::PoolPayloads *pvp = pairs ? &pv : nullptr;
-    const vrs::PoolStreams ps = vrs::pool_streams(n);
     const uint32_t c = st.cur;
     uint32_t *home = static_cast<uint32_t *>(st.kptr[c]), *partner = static_cast<uint32_t *>(st.kptr[c ^ 1u]);
     vrs::LaunchEvents ev;
     st.cur_at_start = c;
     st.blind_passes = 0;
-    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
-    st.stamp = ctx->os_stamp;
+    st.stamp = next_stamp(ctx);
     // Everything is enqueued here, before any verdict is known (the workgroups of what a verdict refuses leave at once): the
     // second verdict falls only when the second pass has run, and a host that enqueued the local sort after it would leave the
     // GPU idle for a round trip.  The form's shape -- bits of the second pass, the local sort's workgroup -- is chosen from n alone
     // (pool_shape: uniform keys, buckets of n / 16384 or n / 32768 + a few per cent); a bucket above the local sort's capacity
     // makes the second pass flag the sort.
     const uint32_t tiles_b = vrs::pool_tiles_b_cap(n);
-    const uint32_t par = (++ctx->os_pool_epoch) & 1u;
-    st.pool_par = par;
+    vrs::PoolForm form{};  // what all launches of the sort share
+    form.n = n;
+    form.key_base = st.key_base;
+    form.ps = vrs::pool_streams(n);
+    form.pool = ctx->os_pool_plan;
+    form.msd = ctx->os_msd_plan;
+    form.par = st.pool_par = (++ctx->os_pool_epoch) & 1u;
+    form.setup = launch_setup(ctx);
+    form.top_bits = top_bits;
+    form.pv = pairs ? &pv : nullptr;
     st.pool_reused = ctx->os_pool_reuse && ctx->os_pool_layout_valid && ctx->os_pool_layout_n == n && ctx->os_pool_layout_base == st.key_base &&
                      (ctx->os_pool_layout_sub_bits >> 8) == top_bits;
     // Back-off: a workload whose distribution changes from sort to sort at equal n (sorted, then random; alternating key ranges) finds
@@ -136,7 +140,11 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     }
     if (!st.pool_reused) {
         if ((rc = profile_events(ctx, VRS_KERNEL_POOL_SAMPLE, &ev))) return rc;
-        VRS_HIP(ctx, vrs::launch_pool_sample(ctx->stream, home, n, st.key_base, ps, ctx->os_pool_plan, room, par, ev, top_bits));
+        vrs::PoolSampleArgs s{};
+        s.form = form;
+        s.keys = home;
+        s.overflow_capacity = room;
+        VRS_HIP(ctx, vrs::launch_pool_sample(ctx->stream, s, ev));
         ctx->os_pool_layout_valid = false;  // (until this sort is known to have been taken)
     } else {
         ctx->os_pool_layout_reuses++;
@@ -144,18 +152,46 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     st.ev_lb_before = ctx->events_used[VRS_KERNEL_LOOKBACK_SCATTER];
     st.ev_ls_before = ctx->events_used[VRS_KERNEL_LOCAL_SORT];
     if ((rc = profile_events(ctx, VRS_KERNEL_POOL_PASS_A, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_pool_pass_a(ctx->stream, home, partner, ctx->os_pool_overflow, n, st.key_base, ps, ctx->os_pool_plan, ctx->os_msd_plan,
-                                         ctx->xcc_map, ctx->os_misplace, room, par, ev, pvp, top_bits));
-    const bool keep_rooms = st.pool_reused && ctx->os_pool_reuse_rooms && (ctx->os_pool_layout_sub_bits & 255u) == shape.sub_bits;
-    VRS_HIP(ctx, vrs::launch_pool_plan(ctx->stream, ctx->os_msd_plan, ctx->os_pool_plan, n, tiles_b, ctx->os_pool_slack_cap, partner, ctx->os_pool_overflow, st.key_base, ps, shape.sub_bits, par,
-                                       nullptr, keep_rooms, top_bits));
+    vrs::PoolPassAArgs pa{};
+    pa.form = form;
+    pa.keys_in = home;
+    pa.keys_out = partner;
+    pa.overflow = ctx->os_pool_overflow;
+    pa.overflow_capacity = room;
+    pa.misplace = ctx->os_misplace;
+    VRS_HIP(ctx, vrs::launch_pool_pass_a(ctx->stream, pa, ev));
+    vrs::PoolPlanArgs pl{};
+    pl.form = form;
+    pl.tiles_b_cap = tiles_b;
+    pl.slack_capacity = ctx->os_pool_slack_cap;
+    pl.regions = partner;
+    pl.overflow = ctx->os_pool_overflow;
+    pl.sub_bits = shape.sub_bits;
+    pl.keep_rooms = st.pool_reused && ctx->os_pool_reuse_rooms && (ctx->os_pool_layout_sub_bits & 255u) == shape.sub_bits;
+    VRS_HIP(ctx, vrs::launch_pool_plan(ctx->stream, pl));
     if ((rc = profile_events(ctx, VRS_KERNEL_POOL_PASS_B, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_pool_pass_b(ctx->stream, partner, ctx->os_pool_overflow, ctx->os_pool_slack, n, ctx->os_msd_plan, ctx->os_pool_plan, tiles_b,
-                                         st.key_base, vrs::pool_local_capacity(shape.local), ctx->os_pool_slack_cap, ctx->xcc_map, st.stamp, shape.sub_bits, par, ev,
-                                         false, pvp, top_bits));
+    vrs::PoolPassBArgs pb{};
+    pb.form = form;
+    pb.regions = partner;
+    pb.overflow = ctx->os_pool_overflow;
+    pb.slack = ctx->os_pool_slack;
+    pb.tiles_b = tiles_b;
+    pb.local_cap = vrs::pool_local_capacity(shape.local);
+    pb.slack_capacity = ctx->os_pool_slack_cap;
+    pb.stamp = st.stamp;
+    pb.sub_bits = shape.sub_bits;
+    VRS_HIP(ctx, vrs::launch_pool_pass_b(ctx->stream, pb, ev));
     if ((rc = profile_events(ctx, VRS_KERNEL_LOCAL_SORT, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_pool_local_sort(ctx->stream, ctx->os_pool_slack, home, n, ctx->os_msd_plan, ctx->os_pool_plan, shape, &ctx->os_plan->head,
-                                             ctx->os_host_head_dev, st.stamp, par, ev, top_bytes, nullptr, false, pvp));
+    vrs::PoolLocalSortArgs ls{};
+    ls.form = form;
+    ls.slack = ctx->os_pool_slack;
+    ls.keys_out = home;
+    ls.shape = shape;
+    ls.dev_head = &ctx->os_plan->head;
+    ls.host_head = ctx->os_host_head_dev;
+    ls.stamp = st.stamp;
+    ls.top_bytes = top_bytes;
+    VRS_HIP(ctx, vrs::launch_pool_local_sort(ctx->stream, ls, ev));
     ctx->os_cursors_open = false;  // the local sort re-arms the reservation counters (a refusal is handled by one_read_complete)
     st.active = true;
     return VRS_OK;

@@ -143,8 +143,8 @@ int one_read_scratch(vrs_context ctx, const vrs_context_t::OneRead &st, const On
         vrs::OnesweepPlan *plan = nullptr;
         vrs::OnesweepPlanHead *host = nullptr, *host_dev = nullptr;
         // one allocation: the digit tables and, behind them, the ticket word of the fused plan
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&tables), (vrs::kDigitTableWords + 64) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(tables, 0, (vrs::kDigitTableWords + 64) * sizeof(uint32_t), ctx->stream);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&tables), kDigitTableBytes);
+        if (e == hipSuccess) e = hipMemsetAsync(tables, 0, kDigitTableBytes, ctx->stream);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&plan), sizeof(vrs::OnesweepPlan));
         if (e == hipSuccess)
             e = hipHostMalloc(reinterpret_cast<void **>(&host), sizeof(vrs::OnesweepPlanHead) + vrs::kMsdLogWords * sizeof(uint32_t),
@@ -167,8 +167,8 @@ int one_read_scratch(vrs_context ctx, const vrs_context_t::OneRead &st, const On
         uint32_t *counts = nullptr;
         vrs::MsdPlan *mp = nullptr;
         vrs::OnesweepPlan *pa = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&counts), vrs::kMsdCountWords * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(counts, 0, vrs::kMsdCountWords * sizeof(uint32_t), ctx->stream);
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&counts), kMsdCountBytes);
+        if (e == hipSuccess) e = hipMemsetAsync(counts, 0, kMsdCountBytes, ctx->stream);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&mp), sizeof(vrs::MsdPlan));
         if (e == hipSuccess) e = hipMemsetAsync(mp, 0, sizeof(vrs::MsdPlan), ctx->stream);  // the reservation counters start at zero
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pa), sizeof(vrs::OnesweepPlan));
@@ -196,17 +196,28 @@ int one_read_scratch(vrs_context ctx, const vrs_context_t::OneRead &st, const On
     return VRS_OK;
 }
 
-int one_read_lookback_pass(vrs_context ctx, vrs_context_t::OneRead &st, uint32_t i, uint32_t shift, uint32_t grid_tiles, bool forced) {
+int one_read_lookback_pass(vrs_context ctx, vrs_context_t::OneRead &st, uint32_t i, uint32_t shift, uint32_t grid_tiles, int forced) {
     const bool pairs = st.vptr[0] != nullptr;
-    void *kin = st.kptr[st.cur], *kout = st.kptr[st.cur ^ 1u];
-    void *vin = pairs ? st.vptr[st.cur] : nullptr, *vout = pairs ? st.vptr[st.cur ^ 1u] : nullptr;
+    vrs::OnesweepScatterArgs a{};
+    a.keys_in = st.kptr[st.cur];
+    a.keys_out = st.kptr[st.cur ^ 1u];
+    a.values_in = pairs ? static_cast<const uint32_t *>(st.vptr[st.cur]) : nullptr;
+    a.values_out = pairs ? static_cast<uint32_t *>(st.vptr[st.cur ^ 1u]) : nullptr;
     st.cur ^= 1u;
     vrs::LaunchEvents ev;
     int r = profile_events(ctx, VRS_KERNEL_LOOKBACK_SCATTER, &ev);
     if (r) return r;
-    VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, kin, kout, static_cast<const uint32_t *>(vin), static_cast<uint32_t *>(vout),
-                                              ctx->os_plan, i, shift, ctx->os_status, grid_tiles, forced, ctx->scatter.atomic_rank,
-                                              ctx->xcc_map, st.key_bytes, ctx->os_spin_budget, ctx->os_hold_tile, ev, ctx->os_misplace, 0, nullptr, drift_word(ctx)));
+    a.plan = ctx->os_plan;
+    a.pass = i;
+    a.shift = shift;
+    a.status = ctx->os_status;
+    a.grid_tiles = grid_tiles;
+    a.forced = forced;
+    a.key_bytes = st.key_bytes;
+    a.setup = launch_setup(ctx);
+    a.hold_tile = ctx->os_hold_tile;
+    a.misplace = ctx->os_misplace;
+    VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, a, ev));
     return VRS_OK;
 }
 
@@ -232,11 +243,21 @@ int one_read_hybrid_tail(vrs_context ctx, vrs_context_t::OneRead &st, const OneR
     vrs::LaunchEvents ev;
     int rc;
     if ((rc = profile_events(ctx, VRS_KERNEL_LOOKBACK_SCATTER, &ev))) return rc;
-    VRS_HIP(ctx, vrs::launch_msd_pass_b(ctx->stream, st.kptr[home ^ 1u], st.kptr[home],
-                                        pairs ? static_cast<const uint32_t *>(st.vptr[home ^ 1u]) : nullptr,
-                                        pairs ? static_cast<uint32_t *>(st.vptr[home]) : nullptr, ctx->os_msd_plan, ctx->os_status,
-                                        tiles_b, ctx->scatter.atomic_rank, ctx->xcc_map, st.key_bytes, ctx->os_spin_budget, ev,
-                                        st.key_base, st.sub_bits, reserves(ctx, st.n, pairs), drift_word(ctx)));
+    uint32_t *values_home = pairs ? static_cast<uint32_t *>(st.vptr[home]) : nullptr;
+    vrs::MsdPassBArgs b{};
+    b.keys_in = st.kptr[home ^ 1u];
+    b.keys_out = st.kptr[home];
+    b.values_in = pairs ? static_cast<const uint32_t *>(st.vptr[home ^ 1u]) : nullptr;
+    b.values_out = values_home;
+    b.msd = ctx->os_msd_plan;
+    b.status = ctx->os_status;
+    b.tiles_b = tiles_b;
+    b.key_bytes = st.key_bytes;
+    b.setup = launch_setup(ctx);
+    b.key_base = st.key_base;
+    b.sub_bits = st.sub_bits;
+    b.reserve = reserves(ctx, st.n, pairs);
+    VRS_HIP(ctx, vrs::launch_msd_pass_b(ctx->stream, b, ev));
     if ((rc = profile_events(ctx, VRS_KERNEL_LOCAL_SORT, &ev))) return rc;
     // Launched with the plan known (it said yes), the local sort also clears the look-back status words -- it is LDS-bound and
     // has HBM time to spare, the next sort's counting read does not.  Launched blind it may leave at once: nothing is promised.
@@ -247,14 +268,26 @@ int one_read_hybrid_tail(vrs_context ctx, vrs_context_t::OneRead &st, const OneR
     const bool untouched = reserves(ctx, st.n, pairs);
     const bool clears = !untouched && (!st.blind_tail || status_was_clean);
     uint32_t *clear = clears ? ctx->os_status : nullptr;
-    const size_t clear_words = clears ? ctx->os_status_rows * VRS_RADIX_SORT_BINS : 0;
-    if (wide)
-        VRS_HIP(ctx, vrs::launch_msd_local_sort_u64(ctx->stream, st.kptr[home], ctx->os_msd_plan, max_bucket, ev, clear, clear_words,
-                                                    pairs ? static_cast<uint32_t *>(st.vptr[home]) : nullptr));
-    else
-        VRS_HIP(ctx, vrs::launch_msd_local_sort(ctx->stream, static_cast<uint32_t *>(st.kptr[home]),
-                                                pairs ? static_cast<uint32_t *>(st.vptr[home]) : nullptr, ctx->os_msd_plan, max_bucket, ev,
-                                                clear, clear_words));
+    const size_t clear_words = clears ? status_words(ctx) : 0;
+    if (wide) {
+        vrs::MsdLocalSortU64Args l{};
+        l.keys = st.kptr[home];
+        l.values = values_home;
+        l.msd = ctx->os_msd_plan;
+        l.max_bucket = max_bucket;
+        l.clear_status = clear;
+        l.clear_words = clear_words;
+        VRS_HIP(ctx, vrs::launch_msd_local_sort_u64(ctx->stream, l, ev));
+    } else {
+        vrs::MsdLocalSortArgs l{};
+        l.keys = static_cast<uint32_t *>(st.kptr[home]);
+        l.values = values_home;
+        l.msd = ctx->os_msd_plan;
+        l.max_bucket = max_bucket;
+        l.clear_status = clear;
+        l.clear_words = clear_words;
+        VRS_HIP(ctx, vrs::launch_msd_local_sort(ctx->stream, l, ev));
+    }
     // (a whole sort enqueued blind may still be refused and run its LSD passes, which write the words, from one_read_complete:
     // it makes no claim)
     if (clear || (untouched && (!st.blind_tail || status_was_clean))) ctx->os_status_clean = true;
@@ -337,44 +370,75 @@ int one_read_enqueue(vrs_context ctx) {
         vrs_context ctx;
         bool armed = false;
         ~TablesGuard() {
-            if (armed) (void)hipMemsetAsync(ctx->os_tables, 0, (vrs::kDigitTableWords + 64) * sizeof(uint32_t), ctx->stream);
-            if (armed && ctx->os_msd_counts)
-                (void)hipMemsetAsync(ctx->os_msd_counts, 0, vrs::kMsdCountWords * sizeof(uint32_t), ctx->stream);
+            if (armed) rearm_counting_tables(ctx);
         }
     } guard{ctx};
     const uint32_t group = st.group;
     // the previous hybrid sort's local sort left the status words cleared (see one_read_hybrid_tail): nothing to zero then
     // ("clean" speaks for the whole allocation -- a sort whose MSD passes reserve leaves the words alone and hands the claim on --
     // so a counting read that has to clear them clears all of them, not just the rows of this sort)
-    const size_t zero_words = ctx->os_status_clean ? 0 : ctx->os_status_rows * VRS_RADIX_SORT_BINS;
+    const size_t zero_words = status_words_to_zero(ctx);
     ctx->os_status_clean = false;  // this sort's passes write them
     if ((rc = profile_events(ctx, VRS_KERNEL_DIGIT_TABLES, &ev))) return rc;
-    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
-    st.stamp = ctx->os_stamp;
+    st.stamp = next_stamp(ctx);
     guard.armed = true;
-    const vrs::FusedPlan fused{ctx->os_plan, ctx->os_host_head_dev, ctx->os_ticket, st.stamp, g.T, g.tile_cap, g.blind_cap, g.cuts0};
+    const vrs::LaunchSetup setup = launch_setup(ctx);
     if (msd) {
         // hybrid: the same read (after probing the key range on a sample) also fills the histogram of the range's top 14
         // bits; ONE plan kernel makes the LSD plan as always, decides which form runs, arms exactly one of the two first
         // passes and stamps the head
-        if (wide)
-            VRS_HIP(ctx, vrs::launch_msd_count_u64(ctx->stream, st.kptr[st.cur], n, g.group_len, ctx->os_status,
-                                                   zero_words, ctx->scatter.compute_units, ctx->os_msd_counts, ev));
-        else
-            VRS_HIP(ctx, vrs::launch_digit_tables_msd(ctx->stream, st.kptr[st.cur], n, g.group_len, ctx->os_tables, ctx->os_status,
-                                                      zero_words, ctx->scatter.compute_units, ctx->os_msd_counts,
-                                                      st.fast_count, ev, st.key_base));
-        VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, ctx->os_msd_counts, ctx->os_msd_plan, ctx->os_plan_a, ctx->os_plan,
-                                          ctx->os_host_head_dev, st.stamp, n, g.T, g.tiles_b_cap, g.local_cap, ctx->os_tables,
-                                          g.group_len, g.tile_cap, g.blind_cap, g.cuts0, wide ? 2u : st.fast_count ? 1u : 0u,
-                                          wide ? 50u : 18u));
+        if (wide) {
+            vrs::MsdCountU64Args c{};
+            c.keys = st.kptr[st.cur];
+            c.n = n;
+            c.group_len = g.group_len;
+            c.status = ctx->os_status;
+            c.status_words = zero_words;
+            c.setup = setup;
+            c.msd_counts = ctx->os_msd_counts;
+            VRS_HIP(ctx, vrs::launch_msd_count_u64(ctx->stream, c, ev));
+        } else {
+            vrs::DigitTablesMsdArgs c{};
+            c.keys = st.kptr[st.cur];
+            c.n = n;
+            c.group_len = g.group_len;
+            c.tables = ctx->os_tables;
+            c.status = ctx->os_status;
+            c.status_words = zero_words;
+            c.setup = setup;
+            c.msd_counts = ctx->os_msd_counts;
+            c.msd_only = st.fast_count;
+            c.key_base = st.key_base;
+            VRS_HIP(ctx, vrs::launch_digit_tables_msd(ctx->stream, c, ev));
+        }
+        vrs::MsdPlanArgs p = msd_plan_args(ctx, g, n, st.stamp);
+        p.msd_only = wide ? vrs::kMsdOnlyWide : st.fast_count ? vrs::kMsdOnlyFastCount : vrs::kMsdOnlyNo;
+        p.max_shift = wide ? 50u : 18u;
+        VRS_HIP(ctx, vrs::launch_msd_plan(ctx->stream, p));
     } else {
-        VRS_HIP(ctx, vrs::launch_digit_tables(ctx->stream, st.kptr[st.cur], n, key_bytes, 32u * group, g.group_len, g.G, ctx->os_tables,
-                                              ctx->os_status, zero_words, ctx->scatter.compute_units, ev,
-                                              ctx->os_fused_plan ? &fused : nullptr));
-        if (!ctx->os_fused_plan)
-            VRS_HIP(ctx, vrs::launch_plan(ctx->stream, ctx->os_tables, ctx->os_plan, ctx->os_host_head_dev, st.stamp, n, g.group_len,
-                                          g.G, g.T, g.tile_cap, g.blind_cap, g.cuts0));
+        vrs::DigitTablesArgs c{};
+        c.keys = st.kptr[st.cur];
+        c.key_bytes = key_bytes;
+        c.base_shift = 32u * group;
+        c.groups = g.G;
+        c.tables = ctx->os_tables;
+        c.status = ctx->os_status;
+        c.status_words = zero_words;
+        c.setup = setup;
+        c.geo = plan_geometry(ctx, g, n, st.stamp);
+        if (ctx->os_fused_plan) {
+            c.fused_plan = ctx->os_plan;
+            c.fused_done = ctx->os_ticket;
+        }
+        VRS_HIP(ctx, vrs::launch_digit_tables(ctx->stream, c, ev));
+        if (!ctx->os_fused_plan) {
+            vrs::PlanArgs p{};
+            p.tables = ctx->os_tables;
+            p.plan = ctx->os_plan;
+            p.groups = g.G;
+            p.geo = c.geo;
+            VRS_HIP(ctx, vrs::launch_plan(ctx->stream, p));
+        }
     }
     guard.armed = false;
     // speculative launches, before the plan is known here.  LSD form: all four passes (pass 0's streams are the host's
@@ -389,15 +453,27 @@ int one_read_enqueue(vrs_context ctx) {
         if (!pairs && (rc = reservation_begin(ctx))) return rc;
         if ((rc = profile_events(ctx, VRS_KERNEL_LOOKBACK_SCATTER, &ev))) return rc;
         const uint32_t c = st.cur_at_start;
-        VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, st.kptr[c], st.kptr[c ^ 1u],
-                                                  pairs ? static_cast<const uint32_t *>(st.vptr[c]) : nullptr,
-                                                  pairs ? static_cast<uint32_t *>(st.vptr[c ^ 1u]) : nullptr, ctx->os_plan_a, 0,
-                                                  vrs::kShiftFromPlan, ctx->os_status, g.tiles0, false, ctx->scatter.atomic_rank,
-                                                  ctx->xcc_map, key_bytes, ctx->os_spin_budget, ctx->os_hold_tile, ev, ctx->os_misplace,
-                                                  st.key_base, reserves(ctx, n, pairs) ? ctx->os_msd_plan : nullptr, drift_word(ctx)));
+        vrs::OnesweepScatterArgs a{};
+        a.keys_in = st.kptr[c];
+        a.keys_out = st.kptr[c ^ 1u];
+        a.values_in = pairs ? static_cast<const uint32_t *>(st.vptr[c]) : nullptr;
+        a.values_out = pairs ? static_cast<uint32_t *>(st.vptr[c ^ 1u]) : nullptr;
+        a.plan = ctx->os_plan_a;
+        a.pass = 0;
+        a.shift = vrs::kShiftFromPlan;
+        a.status = ctx->os_status;
+        a.grid_tiles = g.tiles0;
+        a.forced = vrs::kForcedNo;
+        a.key_bytes = key_bytes;
+        a.setup = setup;
+        a.hold_tile = ctx->os_hold_tile;
+        a.misplace = ctx->os_misplace;
+        a.key_base = st.key_base;
+        a.reserve = reserves(ctx, n, pairs) ? ctx->os_msd_plan : nullptr;
+        VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, a, ev));
     }
     for (uint32_t i = 0; i < st.blind_passes; ++i)
-        if ((rc = one_read_lookback_pass(ctx, st, i, 32u * group + 8u * i, i == 0 ? g.tiles0 : g.blind_cap, false))) return rc;
+        if ((rc = one_read_lookback_pass(ctx, st, i, 32u * group + 8u * i, i == 0 ? g.tiles0 : g.blind_cap, vrs::kForcedNo))) return rc;
     if (msd && st.blind_tail && (rc = one_read_hybrid_tail(ctx, st, g, g.tiles_b_cap, g.local_cap))) return rc;
     st.active = true;
     return VRS_OK;
@@ -451,23 +527,34 @@ int one_read_complete(vrs_context ctx, bool *done) {
             if (local != 99u) {
                 vrs::LaunchEvents ev;
                 if ((rc = profile_events(ctx, VRS_KERNEL_LOCAL_SORT, &ev))) return rc;
-                if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
-                st.stamp = ctx->os_stamp;
+                st.stamp = next_stamp(ctx);
                 vrs::PoolPayloads pv{};
                 if (pairs) {
                     pv.values_home = static_cast<uint32_t *>(st.vptr[st.cur_at_start]);
                     pv.slack_values = ctx->os_pool_slack_vals;
                     pv.status = ctx->os_status;
-                    pv.status_words = ctx->os_status_rows * VRS_RADIX_SORT_BINS;
+                    pv.status_words = status_words(ctx);
                     pv.top_bits = st.pool_top_bits;
                     pv.packed = ctx->os_pool_pairs_packed;
                 }
                 st.pool_retried = true;
                 st.pool_local = local;
                 ctx->os_pool_retries++;
-                VRS_HIP(ctx, vrs::launch_pool_local_sort(ctx->stream, ctx->os_pool_slack, static_cast<uint32_t *>(st.kptr[st.cur_at_start]), n, ctx->os_msd_plan,
-                                                         ctx->os_pool_plan, vrs::PoolShape{st.pool_sub_bits, local}, &ctx->os_plan->head, ctx->os_host_head_dev,
-                                                         st.stamp, st.pool_par, ev, 1u << st.pool_top_bits, nullptr, true, pairs ? &pv : nullptr));
+                vrs::PoolLocalSortArgs l{};
+                l.form.n = n;
+                l.form.pool = ctx->os_pool_plan;
+                l.form.msd = ctx->os_msd_plan;
+                l.form.par = st.pool_par;
+                l.form.pv = pairs ? &pv : nullptr;
+                l.slack = ctx->os_pool_slack;
+                l.keys_out = static_cast<uint32_t *>(st.kptr[st.cur_at_start]);
+                l.shape = vrs::PoolShape{st.pool_sub_bits, local};
+                l.dev_head = &ctx->os_plan->head;
+                l.host_head = ctx->os_host_head_dev;
+                l.stamp = st.stamp;
+                l.top_bytes = 1u << st.pool_top_bits;
+                l.retry = true;
+                VRS_HIP(ctx, vrs::launch_pool_local_sort(ctx->stream, l, ev));
                 return VRS_OK;  // (still active: the settle waits for this one's word)
             }
         }
@@ -561,7 +648,7 @@ int one_read_complete(vrs_context ctx, bool *done) {
             } else {
                 ctx->os_lookback_passes++;
                 if (i < st.blind_passes) ctx->os_relaunched_passes++;
-                if ((rc = one_read_lookback_pass(ctx, st, i, shift, head.max_tiles[i], true))) return rc;
+                if ((rc = one_read_lookback_pass(ctx, st, i, shift, head.max_tiles[i], vrs::kForcedYes))) return rc;
             }
         }
     }
@@ -582,8 +669,7 @@ int one_read_settle(vrs_context ctx) {
         if (rc == VRS_ERROR_TIMEOUT) return rc;  // still pending: a later settle may succeed
         if (rc) {  // the plan never arrived / the stream faulted: nothing to resume, and the next sort must not find this one "pending"
             ctx->one_read.active = false;
-            if (ctx->os_tables) (void)hipMemsetAsync(ctx->os_tables, 0, (vrs::kDigitTableWords + 64) * sizeof(uint32_t), ctx->stream);
-            if (ctx->os_msd_counts) (void)hipMemsetAsync(ctx->os_msd_counts, 0, vrs::kMsdCountWords * sizeof(uint32_t), ctx->stream);
+            rearm_counting_tables(ctx);
             ctx->os_cursors_open = true;
             return rc;
         }

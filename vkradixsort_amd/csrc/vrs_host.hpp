@@ -212,6 +212,10 @@ struct OneReadGeometry {
     vrs::StreamCuts cuts0;
 };
 
+// the digit tables with the fused plan's ticket word behind them / the hybrid form's counts: one allocation each, zero between sorts
+constexpr size_t kDigitTableBytes = (vrs::kDigitTableWords + 64) * sizeof(uint32_t);
+constexpr size_t kMsdCountBytes = vrs::kMsdCountWords * sizeof(uint32_t);
+
 constexpr int kPoolNoMemory = -4242;  // (internal: pool_scratch found no room on the device; never leaves the library)
 
 int fail(vrs_context ctx, int code, const std::string &msg);
@@ -237,8 +241,62 @@ int wait_for_host_word(vrs_context ctx, const std::function<bool()> &arrived, bo
 int wait_for_plan(vrs_context ctx, uint32_t stamp);
 vrs_buffer_t stack_view(vrs_context ctx, void *ptr, size_t bytes);
 OneReadGeometry one_read_geometry(vrs_context ctx, const vrs_context_t::OneRead &st);
+// the stamp of the next plan (never 0)
+inline uint32_t next_stamp(vrs_context ctx) {
+    if (++ctx->os_stamp == 0) ctx->os_stamp = 1;
+    return ctx->os_stamp;
+}
+// the look-back status words the context owns / those a counting read has to zero (none while every word is known to be zero)
+inline size_t status_words(vrs_context ctx) { return ctx->os_status_rows * VRS_RADIX_SORT_BINS; }
+inline size_t status_words_to_zero(vrs_context ctx) { return ctx->os_status_clean ? 0 : status_words(ctx); }
+// the digit tables and the hybrid form's counts must be all zero when a counting read starts: after a failure between a counting
+// read and its plan, re-arm them for the next sort (best effort: the caller is already on an error path)
+inline void rearm_counting_tables(vrs_context ctx) {
+    if (ctx->os_tables) (void)hipMemsetAsync(ctx->os_tables, 0, kDigitTableBytes, ctx->stream);
+    if (ctx->os_msd_counts) (void)hipMemsetAsync(ctx->os_msd_counts, 0, kMsdCountBytes, ctx->stream);
+}
+// what every launch of this context is given (the test hooks os_hold_tile / os_misplace are NOT part of it: each call site says
+// whether they apply)
+inline vrs::LaunchSetup launch_setup(vrs_context ctx) {
+    vrs::LaunchSetup s{};
+    s.atomic_rank = ctx->scatter.atomic_rank;
+    s.xcc_map = ctx->xcc_map;
+    s.spin_budget = ctx->os_spin_budget;
+    s.drift = drift_word(ctx);
+    s.compute_units = ctx->scatter.compute_units;
+    return s;
+}
+// what the plan of a counting read over n keys is made from: the one place the sort's geometry becomes launcher arguments
+inline vrs::PlanGeometry plan_geometry(vrs_context ctx, const OneReadGeometry &g, uint32_t n, uint32_t stamp) {
+    vrs::PlanGeometry p{};
+    p.n = n;
+    p.group_len = g.group_len;
+    p.tile = g.T;
+    p.tile_cap = g.tile_cap;
+    p.blind_cap = g.blind_cap;
+    p.cuts0 = g.cuts0;
+    p.stamp = stamp;
+    p.host_head = ctx->os_host_head_dev;
+    return p;
+}
+// launch_msd_plan's arguments as every caller gives them; the caller sets what differs: msd_only, max_shift (and, where they are
+// not the defaults, msd_counts, host_log, sub_bits)
+inline vrs::MsdPlanArgs msd_plan_args(vrs_context ctx, const OneReadGeometry &g, uint32_t n, uint32_t stamp) {
+    vrs::MsdPlanArgs a{};
+    a.msd_counts = ctx->os_msd_counts;
+    a.msd = ctx->os_msd_plan;
+    a.plan_a = ctx->os_plan_a;
+    a.plan_lsd = ctx->os_plan;
+    a.geo = plan_geometry(ctx, g, n, stamp);
+    a.tiles_b_cap = g.tiles_b_cap;
+    a.local_cap = g.local_cap;
+    a.tables = ctx->os_tables;
+    return a;
+}
+// the log of the vrs_msd_finish_* plans' decisions (kMsdLogWords words behind the pinned host head), as the device sees it
+inline uint32_t *finish_log(vrs_context ctx) { return reinterpret_cast<uint32_t *>(ctx->os_host_head_dev + 1); }
 int one_read_scratch(vrs_context ctx, const vrs_context_t::OneRead &st, const OneReadGeometry &g);
-int one_read_lookback_pass(vrs_context ctx, vrs_context_t::OneRead &st, uint32_t i, uint32_t shift, uint32_t grid_tiles, bool forced);
+int one_read_lookback_pass(vrs_context ctx, vrs_context_t::OneRead &st, uint32_t i, uint32_t shift, uint32_t grid_tiles, int forced);
 bool reserves(vrs_context ctx, uint32_t n, bool pairs);
 int reservation_begin(vrs_context ctx);
 int one_read_hybrid_tail(vrs_context ctx, vrs_context_t::OneRead &st, const OneReadGeometry &g, uint32_t tiles_b, uint32_t max_bucket,

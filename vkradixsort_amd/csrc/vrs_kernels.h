@@ -132,42 +132,82 @@ __host__ __device__ inline uint32_t balanced_cut(const StartOf &start_of, uint32
 StreamCuts pass0_stream_cuts(uint32_t n, uint32_t group_len, uint32_t groups);
 // keys per look-back tile: 8192 uint32 or 4096 uint64 (32 KiB either way)
 uint32_t onesweep_tile_keys(int key_bytes);
+struct MsdPlan;
+// ---- arguments of the launch wrappers below: one aggregate of named fields per launcher, filled field by field at the call
+// site (`XArgs a{}; a.field = ...;`).  A member with an initialiser has that default; every call site sets the others.
+// What is the same at every launch of one context (vrsh::launch_setup, vrs_host.hpp, reads it off the context once per entry point).
+struct LaunchSetup {
+    bool atomic_rank;            // rank with returning LDS atomics (ScatterLaunch::atomic_rank; only after the device self-test passed)
+    unsigned long long xcc_map;  // byte x = the XCC the placement probe found blocks b % 8 == x on
+    uint32_t spin_budget;        // polls of an unpublished look-back row before a tile stops waiting and counts its stream's earlier keys itself
+    uint32_t *drift;             // a word of pinned host memory (device view) the first blocks add to when they find themselves on another XCC
+                                 // than xcc_map says (report_drift, vrs_device.hpp), or nullptr
+    int compute_units;           // the counting reads: one grid that fills the chip once
+};
+// What a plan is made from: the same for the fused plan of launch_digit_tables, launch_plan and launch_msd_plan
+// (vrsh::plan_geometry, vrs_host.hpp, fills it from the sort's OneReadGeometry).
+struct PlanGeometry {
+    uint32_t n;
+    uint32_t group_len;           // keys per pass-0 group (whole tiles)
+    uint32_t tile;                // keys per look-back tile (onesweep_tile_keys)
+    uint32_t tile_cap;            // rows of workgroups a look-back pass may need: a stream longer than tile_cap tiles makes its pass kPassUnbalanced
+    uint32_t blind_cap;           // rows of workgroups of the speculatively enqueued passes 1-3 (<= tile_cap)
+    StreamCuts cuts0;             // pass 0's streams (pass0_stream_cuts)
+    uint32_t stamp;               // the sort's stamp (never 0): the last word the plan writes into the host head
+    OnesweepPlanHead *host_head;  // device-visible address of a pinned host copy of the head (written with system-scope stores, `stamp` last)
+};
 // Look-back status words: ONE region of kStreams * tile_cap rows of 256 words serves all four passes of a group --
 // a word carries the pass's tag, so only the counting read zeroes it (once per group of four passes).
 // Counts the four digits at bits [base_shift, base_shift + 32) of every key into tables[4][groups][256]; also zeroes
-// status[0, status_words) (a multiple of 4 words, 16-byte aligned).  group_len: keys per pass-0 group (whole tiles).
-// fused: the counting read's last workgroup also makes the plan (what launch_plan would do in a launch of its own);
-// done = a zero-initialised ticket word the launches share
-struct FusedPlan {
-    OnesweepPlan *plan;
-    OnesweepPlanHead *host_head;
-    uint32_t *done;
-    uint32_t stamp, tile, tile_cap, blind_cap;
-    StreamCuts cuts0;
+// status[0, status_words) (a multiple of 4 words, 16-byte aligned).
+struct DigitTablesArgs {
+    const void *keys;
+    int key_bytes;
+    uint32_t base_shift;
+    uint32_t groups;
+    uint32_t *tables;
+    uint32_t *status;
+    size_t status_words;
+    LaunchSetup setup;   // compute_units
+    PlanGeometry geo;    // n and group_len; fused: all of it
+    // fused: the counting read's last workgroup also makes the plan (what launch_plan would do in a launch of its own);
+    // fused_done = a zero-initialised ticket word the launches share.  nullptr: the plan is a launch of its own
+    OnesweepPlan *fused_plan = nullptr;
+    uint32_t *fused_done = nullptr;
 };
-hipError_t launch_digit_tables(hipStream_t stream, const void *keys, uint32_t n, int key_bytes, uint32_t base_shift,
-                               uint32_t group_len, uint32_t groups, uint32_t *tables, uint32_t *status,
-                               size_t status_words, int compute_units, LaunchEvents ev = {},
-                               const FusedPlan *fused = nullptr);
-// host_head: device-visible address of a pinned host copy of the head (written with system-scope stores, `stamp` last)
-// blind_cap: rows of workgroups of the speculatively enqueued passes 1-3 (<= tile_cap)
-hipError_t launch_plan(hipStream_t stream, uint32_t *tables, OnesweepPlan *plan, OnesweepPlanHead *host_head,
-                       uint32_t stamp, uint32_t n, uint32_t group_len, uint32_t groups, uint32_t tile, uint32_t tile_cap,
-                       uint32_t blind_cap, const StreamCuts &cuts0);
-// pass = 0..3 inside the group of four the plan was made for, shift = the pass's absolute bit position; the streams
-// come from plan->head (device memory).  grid_tiles: rows of workgroups to launch (>= the pass's max_tiles, which the
-// host may not know yet: tile_cap).  forced: 1 = run even if the plan marks an earlier pass abnormal (the host's second
-// enqueue); 2 = the same, unless the plan's counts are void (OnesweepPlanHead::msd_counted == 0: the workgroups leave at once).  status: kStreams * grid_tiles rows of 256 tagged words.  spin_budget: polls of an unpublished row before
-// a tile stops waiting and counts its stream's earlier keys itself; hold_tile >= 0: test hook, that tile of every
-// stream never publishes.
-hipError_t launch_onesweep_scatter(hipStream_t stream, const void *keys_in, void *keys_out, const uint32_t *values_in,
-                                   uint32_t *values_out, const OnesweepPlan *plan, uint32_t pass, uint32_t shift,
-                                   uint32_t *status, uint32_t grid_tiles, int forced, bool atomic_rank,
-                                   unsigned long long xcc_map, int key_bytes, uint32_t spin_budget, int hold_tile,
-                                   LaunchEvents ev = {}, bool misplace = false, uint32_t key_base = 0, struct MsdPlan *reserve = nullptr,
-                                   uint32_t *drift = nullptr);
-// drift: a word of pinned host memory (device view) the first blocks add to when they find themselves on another XCC than xcc_map says
-// (report_drift, vrs_device.hpp), or nullptr
+hipError_t launch_digit_tables(hipStream_t stream, const DigitTablesArgs &a, LaunchEvents ev = {});
+struct PlanArgs {
+    uint32_t *tables;
+    OnesweepPlan *plan;
+    uint32_t groups;
+    PlanGeometry geo;
+};
+hipError_t launch_plan(hipStream_t stream, const PlanArgs &a);
+// OnesweepScatterArgs::forced
+enum : int {
+    kForcedNo = 0,
+    kForcedYes = 1,        // run even if the plan marks an earlier pass abnormal (the host's second enqueue)
+    kForcedIfCounted = 2,  // the same, unless the plan's counts are void (OnesweepPlanHead::msd_counted == 0: the workgroups leave at once)
+};
+struct OnesweepScatterArgs {
+    const void *keys_in;
+    void *keys_out;
+    const uint32_t *values_in;  // uint32 payloads that follow their keys (nullptr: keys only)
+    uint32_t *values_out;
+    const OnesweepPlan *plan;   // the streams come from plan->head (device memory)
+    uint32_t pass;              // 0..3 inside the group of four the plan was made for
+    uint32_t shift;             // the pass's absolute bit position (kShiftFromPlan: plan->head.msd_shift_a)
+    uint32_t *status;           // kStreams * grid_tiles rows of 256 tagged words
+    uint32_t grid_tiles;        // rows of workgroups to launch (>= the pass's max_tiles, which the host may not know yet: tile_cap)
+    int forced;                 // kForcedNo / kForcedYes / kForcedIfCounted
+    int key_bytes;
+    LaunchSetup setup;          // atomic_rank, xcc_map, spin_budget, drift
+    int hold_tile = -1;         // >= 0: test hook, that tile of every stream never publishes
+    bool misplace = false;      // test hook, odd rows of workgroups walk the neighbouring stream
+    uint32_t key_base = 0;      // see MsdPassBArgs::key_base
+    MsdPlan *reserve = nullptr;  // the first MSD pass over bare keys takes its places by reservation (MsdPlan::cursor_a), or nullptr
+};
+hipError_t launch_onesweep_scatter(hipStream_t stream, const OnesweepScatterArgs &a, LaunchEvents ev = {});
 // ---- hybrid form of the one-call sort (K5b, uint32 keys): MSD partition by the top 14 bits in two look-back passes,
 // then one workgroup per bucket sorts the low 18 bits inside LDS.
 constexpr uint32_t kMsdBucketCount = 1u << 14;
@@ -199,50 +239,104 @@ static_assert(offsetof(MsdPlan, back_a) == offsetof(MsdPlan, cursor_a) + sizeof(
 constexpr size_t kMsdCountWords = kMsdBucketCount + 8u * 256u + 64u;  // + the probed shift and the out-of-range flag
 constexpr uint32_t kShiftFromPlan = 0xFFFFFFFFu;  // launch_onesweep_scatter: take the shift from plan->head.msd_shift_a
 
-// same as launch_digit_tables with 8 groups, and fills msd_counts (uint32 keys only); msd_only (fast count): a key range
-// the hybrid form can take gets ONLY the bucket histogram -- launch_msd_plan must be told the same
-hipError_t launch_digit_tables_msd(hipStream_t stream, const void *keys, uint32_t n, uint32_t group_len, uint32_t *tables,
-                                   uint32_t *status, size_t status_words, int compute_units, uint32_t *msd_counts,
-                                   bool msd_only, LaunchEvents ev = {}, uint32_t key_base = 0, uint32_t force_shift = 0);
-// force_shift != 0: no range probe, bucket = (key - key_base) >> force_shift (a caller that knows the range: keys grouped by
-// top byte, vrs_msd_finish_grouped_u32)
+// same as launch_digit_tables with 8 groups, and fills msd_counts (uint32 keys only)
+struct DigitTablesMsdArgs {
+    const void *keys;
+    uint32_t n;
+    uint32_t group_len;
+    uint32_t *tables;
+    uint32_t *status;
+    size_t status_words;
+    LaunchSetup setup;         // compute_units
+    uint32_t *msd_counts;
+    bool msd_only;             // (fast count) a key range the hybrid form can take gets ONLY the bucket histogram -- launch_msd_plan must be told the same (kMsdOnlyFastCount)
+    uint32_t key_base = 0;     // see MsdPassBArgs::key_base
+    uint32_t force_shift = 0;  // != 0: no range probe, bucket = (key - key_base) >> force_shift (a caller that knows the range: keys grouped by
+                               // top byte, vrs_msd_finish_grouped_u32)
+};
+hipError_t launch_digit_tables_msd(hipStream_t stream, const DigitTablesMsdArgs &a, LaunchEvents ev = {});
 // ONE workgroup: the plan of the four LSD passes (what launch_plan does, 8 groups), then the hybrid form's: bucket
 // offsets, the first MSD pass's seeds (into plan_a->group_seed[0]) and streams, the second pass's tile tables; decides
 // msd_ok (key range 27-32 bits and fully probed, largest bucket <= the local sort's capacity, XCD tile counts <=
 // tiles_b_cap), arms exactly one of the two speculative first passes (plan_a's or plan_lsd's blind descriptors), writes the
-// host head and stamps it.  max_shift: the most low bits the local sort takes (18; 64-bit keys: 50).  msd_only (1: as the
-// counting read was told; 2: 64-bit keys, never any tables): without LSD tables there is no LSD plan -- if msd_ok is 0 then, head.lsd_missing is 1
-// and neither first pass is armed (the caller counts again, for the LSD passes)
-hipError_t launch_msd_plan(hipStream_t stream, uint32_t *msd_counts, MsdPlan *msd, OnesweepPlan *plan_a,
-                           OnesweepPlan *plan_lsd, OnesweepPlanHead *host_head, uint32_t stamp, uint32_t n, uint32_t tile,
-                           uint32_t tiles_b_cap, uint32_t local_cap, uint32_t *tables, uint32_t group_len, uint32_t tile_cap,
-                           uint32_t blind_cap, const StreamCuts &cuts0, uint32_t msd_only, uint32_t max_shift,
-                           uint32_t *host_log = nullptr, uint32_t sub_bits = 6);
-// sub_bits: the low bits of the 14-bit bucket index the second MSD pass sorts by; the input of that pass is grouped by the
-// remaining 14 - sub_bits high bits (a whole sort: 8 + 6, pass A's digit + pass B's)
-// host_log: kMsdLogWords words of pinned host memory (device view) or nullptr; word stamp % kMsdLogWords receives
-// (stamp << 1) | msd_ok before the head's stamp
+// host head and stamps it.
+// MsdPlanArgs::msd_only: without LSD tables there is no LSD plan -- if msd_ok is 0 then, head.lsd_missing is 1 and neither
+// first pass is armed (the caller counts again, for the LSD passes)
+enum : uint32_t {
+    kMsdOnlyNo = 0,
+    kMsdOnlyFastCount = 1,  // as the counting read was told (DigitTablesMsdArgs::msd_only)
+    kMsdOnlyWide = 2,       // 64-bit keys, never any tables
+};
 constexpr uint32_t kMsdLogWords = 32;
+struct MsdPlanArgs {
+    uint32_t *msd_counts;
+    MsdPlan *msd;
+    OnesweepPlan *plan_a;
+    OnesweepPlan *plan_lsd;
+    PlanGeometry geo;
+    uint32_t tiles_b_cap;
+    uint32_t local_cap;
+    uint32_t *tables;
+    uint32_t msd_only;   // kMsdOnlyNo / kMsdOnlyFastCount / kMsdOnlyWide
+    uint32_t max_shift;  // the most low bits the local sort takes (18; 64-bit keys: 50)
+    // kMsdLogWords words of pinned host memory (device view) or nullptr; word stamp % kMsdLogWords receives
+    // (stamp << 1) | msd_ok before the head's stamp
+    uint32_t *host_log = nullptr;
+    // the low bits of the 14-bit bucket index the second MSD pass sorts by; the input of that pass is grouped by the
+    // remaining 14 - sub_bits high bits (a whole sort: 8 + 6, pass A's digit + pass B's)
+    uint32_t sub_bits = 6;
+};
+hipError_t launch_msd_plan(hipStream_t stream, const MsdPlanArgs &a);
 // second MSD pass: bits [18, 24) inside every top-byte bucket; grid of 8 * tiles_b workgroups; status rows: 8 * tiles_b
-// values_in / values_out: uint32 payloads that follow their keys (nullptr: keys only)
-hipError_t launch_msd_pass_b(hipStream_t stream, const void *keys_in, void *keys_out, const uint32_t *values_in,
-                             uint32_t *values_out, MsdPlan *msd, uint32_t *status, uint32_t tiles_b, bool atomic_rank,
-                             unsigned long long xcc_map, int key_bytes, uint32_t spin_budget, LaunchEvents ev = {}, uint32_t key_base = 0, uint32_t sub_bits = 6,
-                             bool reserve = false, uint32_t *drift = nullptr);
-// key_base (uint32 keys of the hybrid form only): the caller promises keys >= key_base (a multiple of 2^24); buckets and MSD
-// digits are taken from key - key_base, so a sub-range of the key space gets the same 16384 buckets a full range would;
-// a key below it makes the counting read flag the sort and the plan refuse the hybrid form
+struct MsdPassBArgs {
+    const void *keys_in;
+    void *keys_out;
+    const uint32_t *values_in;  // uint32 payloads that follow their keys (nullptr: keys only)
+    uint32_t *values_out;
+    MsdPlan *msd;
+    uint32_t *status;
+    uint32_t tiles_b;
+    int key_bytes;
+    LaunchSetup setup;  // atomic_rank, xcc_map, spin_budget, drift
+    // (uint32 keys of the hybrid form only): the caller promises keys >= key_base (a multiple of 2^24); buckets and MSD
+    // digits are taken from key - key_base, so a sub-range of the key space gets the same 16384 buckets a full range would;
+    // a key below it makes the counting read flag the sort and the plan refuse the hybrid form
+    uint32_t key_base = 0;
+    uint32_t sub_bits = 6;  // see MsdPlanArgs::sub_bits
+    bool reserve = false;   // bare keys: the tiles take their places by reservation (MsdPlan::cursor_b) instead of looking back
+};
+hipError_t launch_msd_pass_b(hipStream_t stream, const MsdPassBArgs &a, LaunchEvents ev = {});
 // 64-bit keys: the counting read of the hybrid form (bucket histogram + top-byte counts of the 8 input slices only; zeroes
 // the status words) and the local sort of every bucket by its low msd->shift bits (ceil(shift / 9) LDS passes)
-hipError_t launch_msd_count_u64(hipStream_t stream, const void *keys, uint32_t n, uint32_t group_len, uint32_t *status,
-                                size_t status_words, int compute_units, uint32_t *msd_counts, LaunchEvents ev = {});
-// clear_status / clear_words (a multiple of 4): look-back status words the kernel clears on the side (for the next sort), or nullptr
-hipError_t launch_msd_local_sort_u64(hipStream_t stream, void *keys, MsdPlan *msd, uint32_t max_bucket, LaunchEvents ev = {},
-                                     uint32_t *clear_status = nullptr, size_t clear_words = 0, uint32_t *values = nullptr);
-// values: uint32 payloads that follow their 64-bit keys (buckets up to msd_local_capacity_pairs_u64(false) elements)
-// max_bucket: the plan's msd_max_bucket (picks the workgroup shape: 256 threads up to 7165 keys, else 512)
-hipError_t launch_msd_local_sort(hipStream_t stream, uint32_t *keys, uint32_t *values, MsdPlan *msd, uint32_t max_bucket,
-                                 LaunchEvents ev = {}, uint32_t *clear_status = nullptr, size_t clear_words = 0);
+struct MsdCountU64Args {
+    const void *keys;
+    uint32_t n;
+    uint32_t group_len;
+    uint32_t *status;
+    size_t status_words;
+    LaunchSetup setup;  // compute_units
+    uint32_t *msd_counts;
+};
+hipError_t launch_msd_count_u64(hipStream_t stream, const MsdCountU64Args &a, LaunchEvents ev = {});
+struct MsdLocalSortU64Args {
+    void *keys;
+    MsdPlan *msd;
+    uint32_t max_bucket;  // see MsdLocalSortArgs::max_bucket
+    // clear_status / clear_words (a multiple of 4): look-back status words the kernel clears on the side (for the next sort), or nullptr
+    uint32_t *clear_status = nullptr;
+    size_t clear_words = 0;
+    uint32_t *values = nullptr;  // uint32 payloads that follow their 64-bit keys (buckets up to msd_local_capacity_pairs_u64(false) elements)
+};
+hipError_t launch_msd_local_sort_u64(hipStream_t stream, const MsdLocalSortU64Args &a, LaunchEvents ev = {});
+struct MsdLocalSortArgs {
+    uint32_t *keys;
+    uint32_t *values;     // uint32 payloads that follow their keys (nullptr: keys only)
+    MsdPlan *msd;
+    uint32_t max_bucket;  // the plan's msd_max_bucket (picks the workgroup shape: 256 threads up to 7165 keys, else 512)
+    uint32_t *clear_status = nullptr;  // as MsdLocalSortU64Args'
+    size_t clear_words = 0;
+};
+hipError_t launch_msd_local_sort(hipStream_t stream, const MsdLocalSortArgs &a, LaunchEvents ev = {});
 // keys the local sort of one bucket can hold (the plan refuses the hybrid form when a bucket has more)
 uint32_t msd_local_capacity_small();  // bare uint32 keys, 256-thread workgroup: 7165
 uint32_t msd_local_capacity_wave();   // bare uint32 keys, one wave per bucket: 1789
@@ -361,36 +455,78 @@ struct PoolGroups {          // keys of every top byte (grouped keys; by value: 
 };
 uint32_t pool_local_capacity(uint32_t local);
 uint32_t pool_tiles_b_cap(uint32_t n);         // rows of workgroups of the second pass (its grid is sized before the plan is known)
-// par: the parity of the context's pool epoch (0 / 1; the same for all kernels of one sort: PoolPlan::fail)
-hipError_t launch_pool_sample(hipStream_t stream, const uint32_t *keys, uint32_t n, uint32_t key_base, const PoolStreams &ps,
-                              PoolPlan *pool, uint32_t overflow_capacity, uint32_t par, LaunchEvents ev = {}, uint32_t top_bits = 8);
-// top_bits (every launcher of the form; lab switch VRS_TUNE_MSD_POOL_TOP_BITS): bits of the first pass's digit, 8 -- or 7, with a second pass of 7
-// keys_out: the partner buffer (n slots); overflow: pool_overflow_capacity(n) slots; cursors: MsdPlan::cursor_a (zero when the pass
-// starts); misplace: test hook, odd rows of workgroups walk the neighbouring slice
-hipError_t launch_pool_pass_a(hipStream_t stream, const uint32_t *keys_in, uint32_t *keys_out, uint32_t *overflow, uint32_t n,
-                              uint32_t key_base, const PoolStreams &ps, PoolPlan *pool, MsdPlan *msd, unsigned long long xcc_map,
-                              bool misplace, uint32_t overflow_capacity, uint32_t par, LaunchEvents ev = {}, const PoolPayloads *pv = nullptr, uint32_t top_bits = 8);
+// What the launches of one pool sort (or one finish of grouped keys) share
+struct PoolForm {
+    uint32_t n;
+    uint32_t key_base;    // see MsdPassBArgs::key_base
+    PoolStreams ps;       // pool_streams(n)
+    PoolPlan *pool;
+    MsdPlan *msd;         // its reservation counters (cursor_a: zero when the first pass starts) and the verdict
+    uint32_t par;         // the parity of the context's pool epoch (0 / 1; the same for all kernels of one sort: PoolPlan::fail)
+    LaunchSetup setup;    // xcc_map
+    uint32_t top_bits = 8;  // (lab switch VRS_TUNE_MSD_POOL_TOP_BITS): bits of the first pass's digit, 8 -- or 7, with a second pass of 7
+    const PoolPayloads *pv = nullptr;  // key + payload pairs (the stable form), or nullptr
+};
+// (sample + layout kernels)
+struct PoolSampleArgs {
+    PoolForm form;  // n, key_base, ps, pool, par, top_bits
+    const uint32_t *keys;
+    uint32_t overflow_capacity;
+};
+hipError_t launch_pool_sample(hipStream_t stream, const PoolSampleArgs &a, LaunchEvents ev = {});
+struct PoolPassAArgs {
+    PoolForm form;
+    const uint32_t *keys_in;
+    uint32_t *keys_out;          // the partner buffer (n slots)
+    uint32_t *overflow;          // pool_overflow_capacity(n) slots
+    uint32_t overflow_capacity;
+    bool misplace;               // test hook, odd rows of workgroups walk the neighbouring slice (ignored for pairs)
+};
+hipError_t launch_pool_pass_a(hipStream_t stream, const PoolPassAArgs &a, LaunchEvents ev = {});
 // after the first pass, one workgroup per top byte: top-byte starts, tile tables, piece rows, the buckets' slack regions (from a
-// sample of the first pass's OUTPUT: regions / overflow), verdict 1 (slack_capacity: slots the slack buffer has)
-hipError_t launch_pool_plan(hipStream_t stream, MsdPlan *msd, PoolPlan *pool, uint32_t n, uint32_t tiles_b_cap, uint32_t slack_capacity,
-                            const uint32_t *regions, const uint32_t *overflow, uint32_t key_base, const PoolStreams &ps, uint32_t sub_bits,
-                            uint32_t par, const PoolGroups *groups = nullptr, bool keep_rooms = false, uint32_t top_bits = 8);
-// groups != nullptr: the second half alone (vrs_msd_finish_grouped_counts_u32) -- `regions` holds keys grouped by top byte, top byte a
-// (counted from key_base >> 24) holds groups->count[a] of them; no first pass ran
-// second pass, regions -> slack buffer: grid of 8 * tiles_b workgroups (tiles_b = pool_tiles_b_cap(n)); local_cap: keys the local
-// sort that follows takes per bucket; slack_capacity: as given to the plan (the last kPoolTile slots take refused runs)
-hipError_t launch_pool_pass_b(hipStream_t stream, const uint32_t *regions, const uint32_t *overflow, uint32_t *slack, uint32_t n, MsdPlan *msd,
-                              PoolPlan *pool, uint32_t tiles_b, uint32_t key_base, uint32_t local_cap, uint32_t slack_capacity,
-                              unsigned long long xcc_map, uint32_t stamp, uint32_t sub_bits, uint32_t par, LaunchEvents ev = {}, bool grouped = false,
-                              const PoolPayloads *pv = nullptr, uint32_t top_bits = 8);
+// sample of the first pass's OUTPUT: regions / overflow), verdict 1
+struct PoolPlanArgs {
+    PoolForm form;  // n, key_base, ps, pool, msd, par, top_bits
+    uint32_t tiles_b_cap;
+    uint32_t slack_capacity;  // slots the slack buffer has
+    const uint32_t *regions;
+    const uint32_t *overflow;
+    uint32_t sub_bits;
+    // groups != nullptr: the second half alone (vrs_msd_finish_grouped_counts_u32) -- `regions` holds keys grouped by top byte, top byte a
+    // (counted from key_base >> 24) holds groups->count[a] of them; no first pass ran (top_bits counts as 8, no rooms are kept)
+    const PoolGroups *groups = nullptr;
+    bool keep_rooms = false;  // a kept layout: the buckets' slack regions stay as the last taken sort's plan made them (nothing is sampled)
+};
+hipError_t launch_pool_plan(hipStream_t stream, const PoolPlanArgs &a);
+// second pass, regions -> slack buffer: grid of 8 * tiles_b workgroups (tiles_b = pool_tiles_b_cap(n))
+struct PoolPassBArgs {
+    PoolForm form;  // n, key_base, pool, msd, par, setup, top_bits, pv
+    const uint32_t *regions;
+    const uint32_t *overflow;
+    uint32_t *slack;
+    uint32_t tiles_b;
+    uint32_t local_cap;       // keys the local sort that follows takes per bucket
+    uint32_t slack_capacity;  // as given to the plan (the last kPoolTile slots take refused runs)
+    uint32_t stamp;           // the sort's stamp (never 0): what a tile's claim is exchanged with
+    uint32_t sub_bits;
+    bool grouped = false;     // the second half alone (PoolPlanArgs::groups)
+};
+hipError_t launch_pool_pass_b(hipStream_t stream, const PoolPassBArgs &a, LaunchEvents ev = {});
 // sorts every bucket from its slack region to keys_out[its exact start ...) with the workgroup shape.local.  Gives verdict 2 (verdict 1, no flag from the passes) = MsdPlan::ok and the host head
 // (msd_ok, lsd_missing = 1, stamped last); re-arms the first pass's reservation counters
-hipError_t launch_pool_local_sort(hipStream_t stream, const uint32_t *slack, uint32_t *keys_out, uint32_t n, MsdPlan *msd, const PoolPlan *pool,
-                                  PoolShape shape, OnesweepPlanHead *dev_head, OnesweepPlanHead *host_head, uint32_t stamp, uint32_t par,
-                                  LaunchEvents ev = {}, uint32_t top_bytes = 256, uint32_t *host_log = nullptr, bool retry = false,
-                                  const PoolPayloads *pv = nullptr);
-// retry: the second attempt after a first local sort found a bucket beyond its shape (PoolPlan::fail bit 1): that bit no longer refuses
-// top_bytes: the top bytes that exist (a sort: 256; the second half alone: the caller's); host_log: see launch_msd_plan
+struct PoolLocalSortArgs {
+    PoolForm form;  // n, pool, msd, par, pv
+    const uint32_t *slack;
+    uint32_t *keys_out;
+    PoolShape shape;
+    OnesweepPlanHead *dev_head;
+    OnesweepPlanHead *host_head;
+    uint32_t stamp;
+    uint32_t top_bytes = 256;      // the top bytes that exist (a sort: 256; the second half alone: the caller's)
+    uint32_t *host_log = nullptr;  // see MsdPlanArgs::host_log
+    bool retry = false;            // the second attempt after a first local sort found a bucket beyond its shape (PoolPlan::fail bit 1): that bit no longer refuses
+};
+hipError_t launch_pool_local_sort(hipStream_t stream, const PoolLocalSortArgs &a, LaunchEvents ev = {});
 
 // out[b] = HW_REG_XCC_ID of block b of a `blocks`-block grid of 512-thread workgroups
 hipError_t launch_xcc_probe(hipStream_t stream, uint32_t *out, uint32_t blocks);

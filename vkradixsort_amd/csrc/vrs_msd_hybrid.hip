@@ -772,26 +772,30 @@ __global__ __launch_bounds__(kLocalPairsU64Threads, 2) void msd_local_sort_pairs
     else local_sort_bucket_pairs_u64<THREADS, ITEMS_MAX>(bucket, bvals, n, passes, s_keys, s_vals, s_hist, s_tmp);
 }
 
-hipError_t launch_msd_plan(hipStream_t stream, uint32_t *msd_counts, MsdPlan *msd, OnesweepPlan *plan_a,
-                           OnesweepPlan *plan_lsd, OnesweepPlanHead *host_head, uint32_t stamp, uint32_t n, uint32_t tile,
-                           uint32_t tiles_b_cap, uint32_t local_cap, uint32_t *tables, uint32_t group_len, uint32_t tile_cap,
-                           uint32_t blind_cap, const StreamCuts &cuts0, uint32_t msd_only, uint32_t max_shift, uint32_t *host_log,
-                           uint32_t sub_bits) {
-#define VRS_MSD_PLAN(SUB)                                                                                                     \
-    hipLaunchKernelGGL(msd_plan_kernel<SUB>, dim3(1), dim3(1024), 0, stream, msd_counts, msd, plan_a, plan_lsd, host_head, stamp, \
-                       n, tile, tiles_b_cap, local_cap, tables, group_len, tile_cap, blind_cap, cuts0, msd_only, max_shift, host_log)
-    if (sub_bits == 6u) VRS_MSD_PLAN(6u);
-    else if (sub_bits == 7u) VRS_MSD_PLAN(7u);
-    else if (sub_bits == 8u) VRS_MSD_PLAN(8u);
+hipError_t launch_msd_plan(hipStream_t stream, const MsdPlanArgs &a) {
+    const PlanGeometry &g = a.geo;
+#define VRS_MSD_PLAN(SUB)                                                                                                               \
+    hipLaunchKernelGGL(msd_plan_kernel<SUB>, dim3(1), dim3(1024), 0, stream, a.msd_counts, a.msd, a.plan_a, a.plan_lsd, g.host_head, g.stamp, \
+                       g.n, g.tile, a.tiles_b_cap, a.local_cap, a.tables, g.group_len, g.tile_cap, g.blind_cap, g.cuts0, a.msd_only, a.max_shift, \
+                       a.host_log)
+    if (a.sub_bits == 6u) VRS_MSD_PLAN(6u);
+    else if (a.sub_bits == 7u) VRS_MSD_PLAN(7u);
+    else if (a.sub_bits == 8u) VRS_MSD_PLAN(8u);
     else return hipErrorInvalidValue;
 #undef VRS_MSD_PLAN
     return hipGetLastError();
 }
 
-hipError_t launch_msd_pass_b(hipStream_t stream, const void *keys_in, void *keys_out, const uint32_t *values_in,
-                             uint32_t *values_out, MsdPlan *msd, uint32_t *status, uint32_t tiles_b, bool atomic_rank,
-                             unsigned long long xcc_map, int key_bytes, uint32_t spin_budget, LaunchEvents ev, uint32_t key_base,
-                             uint32_t sub_bits, bool reserve, uint32_t *drift) {
+hipError_t launch_msd_pass_b(hipStream_t stream, const MsdPassBArgs &a, LaunchEvents ev) {
+    const void *keys_in = a.keys_in;
+    void *keys_out = a.keys_out;
+    const uint32_t *values_in = a.values_in;
+    uint32_t *values_out = a.values_out, *status = a.status, *drift = a.setup.drift;
+    MsdPlan *msd = a.msd;
+    const uint32_t tiles_b = a.tiles_b, spin_budget = a.setup.spin_budget, key_base = a.key_base, sub_bits = a.sub_bits;
+    const int key_bytes = a.key_bytes;
+    const bool atomic_rank = a.setup.atomic_rank, reserve = a.reserve;
+    const unsigned long long xcc_map = a.setup.xcc_map;
     if (tiles_b == 0) return hipSuccess;
     if (sub_bits < 6u || sub_bits > 8u) return hipErrorInvalidValue;
     const dim3 grid(8 * tiles_b), block(512);
@@ -816,18 +820,21 @@ hipError_t launch_msd_pass_b(hipStream_t stream, const void *keys_in, void *keys
     return hipGetLastError();
 }
 
-hipError_t launch_msd_count_u64(hipStream_t stream, const void *keys, uint32_t n, uint32_t group_len, uint32_t *status,
-                                size_t status_words, int compute_units, uint32_t *msd_counts, LaunchEvents ev) {
-    const uint32_t wgs = static_cast<uint32_t>(compute_units);
+hipError_t launch_msd_count_u64(hipStream_t stream, const MsdCountU64Args &a, LaunchEvents ev) {
+    const uint32_t wgs = static_cast<uint32_t>(a.setup.compute_units);
     const uint32_t slices = floor_pow2(wgs / 8u > 0 ? wgs / 8u : 1u);
-    VRS_LAUNCH(msd_count_u64_kernel, dim3(8 * slices), dim3(1024), stream, ev, static_cast<const uint64_t *>(keys), n, group_len,
-               slices, reinterpret_cast<uint4 *>(status), static_cast<uint32_t>(status_words / 4), msd_counts,
-               msd_counts + kMsdBuckets);
+    VRS_LAUNCH(msd_count_u64_kernel, dim3(8 * slices), dim3(1024), stream, ev, static_cast<const uint64_t *>(a.keys), a.n, a.group_len,
+               slices, reinterpret_cast<uint4 *>(a.status), static_cast<uint32_t>(a.status_words / 4), a.msd_counts,
+               a.msd_counts + kMsdBuckets);
     return hipGetLastError();
 }
 
-hipError_t launch_msd_local_sort_u64(hipStream_t stream, void *keys, MsdPlan *msd, uint32_t max_bucket, LaunchEvents ev,
-                                     uint32_t *clear_status, size_t clear_words, uint32_t *values) {
+hipError_t launch_msd_local_sort_u64(hipStream_t stream, const MsdLocalSortU64Args &a, LaunchEvents ev) {
+    void *keys = a.keys;
+    uint32_t *values = a.values, *clear_status = a.clear_status;
+    MsdPlan *msd = a.msd;
+    const uint32_t max_bucket = a.max_bucket;
+    const size_t clear_words = a.clear_words;
     if (max_bucket > (values ? kLocalCapPairsU64 : kLocalCapBig)) return hipErrorInvalidValue;  // the plan would have refused
     const StatusClear sc{reinterpret_cast<uint4 *>(clear_status), static_cast<uint32_t>(clear_words / 4)};
     if (values != nullptr) {
@@ -844,8 +851,11 @@ hipError_t launch_msd_local_sort_u64(hipStream_t stream, void *keys, MsdPlan *ms
     return hipGetLastError();
 }
 
-hipError_t launch_msd_local_sort(hipStream_t stream, uint32_t *keys, uint32_t *values, MsdPlan *msd, uint32_t max_bucket,
-                                 LaunchEvents ev, uint32_t *clear_status, size_t clear_words) {
+hipError_t launch_msd_local_sort(hipStream_t stream, const MsdLocalSortArgs &a, LaunchEvents ev) {
+    uint32_t *keys = a.keys, *values = a.values, *clear_status = a.clear_status;
+    MsdPlan *msd = a.msd;
+    const uint32_t max_bucket = a.max_bucket;
+    const size_t clear_words = a.clear_words;
     if (max_bucket > msd_local_capacity(values != nullptr)) return hipErrorInvalidValue;  // the plan would have refused
     const StatusClear sc{reinterpret_cast<uint4 *>(clear_status), static_cast<uint32_t>(clear_words / 4)};
     if (values != nullptr && max_bucket > kLocalCap)

@@ -848,8 +848,11 @@ __global__ __launch_bounds__(512, PAIRS ? 4 : 6) void pool_pass_b_kernel(const u
 // ---------------------------------------------------------------------------------------------
 // host side
 
-hipError_t launch_pool_sample(hipStream_t stream, const uint32_t *keys, uint32_t n, uint32_t key_base, const PoolStreams &ps,
-                              PoolPlan *pool, uint32_t overflow_capacity, uint32_t par, LaunchEvents ev, uint32_t top_bits) {
+hipError_t launch_pool_sample(hipStream_t stream, const PoolSampleArgs &a, LaunchEvents ev) {
+    const uint32_t *keys = a.keys;
+    const uint32_t n = a.form.n, key_base = a.form.key_base, overflow_capacity = a.overflow_capacity, par = a.form.par, top_bits = a.form.top_bits;
+    const PoolStreams &ps = a.form.ps;
+    PoolPlan *pool = a.form.pool;
     if (n == 0 || ps.tiles_per_stream < kPoolSampleTiles) return hipErrorInvalidValue;  // (a sample workgroup's tiles span at most two slices)
     const uint32_t grid = (ps.tiles_total + kPoolSampleTiles - 1u) / kPoolSampleTiles;
     VRS_LAUNCH(pool_sample_kernel, dim3(grid), dim3(256), stream, ev, keys, n, key_base, ps, pool, top_bits);
@@ -857,9 +860,16 @@ hipError_t launch_pool_sample(hipStream_t stream, const uint32_t *keys, uint32_t
     return hipGetLastError();
 }
 
-hipError_t launch_pool_pass_a(hipStream_t stream, const uint32_t *keys_in, uint32_t *keys_out, uint32_t *overflow, uint32_t n,
-                              uint32_t key_base, const PoolStreams &ps, PoolPlan *pool, MsdPlan *msd, unsigned long long xcc_map,
-                              bool misplace, uint32_t overflow_capacity, uint32_t par, LaunchEvents ev, const PoolPayloads *pv, uint32_t top_bits) {
+hipError_t launch_pool_pass_a(hipStream_t stream, const PoolPassAArgs &a, LaunchEvents ev) {
+    const uint32_t *keys_in = a.keys_in;
+    uint32_t *keys_out = a.keys_out, *overflow = a.overflow;
+    const uint32_t n = a.form.n, key_base = a.form.key_base, overflow_capacity = a.overflow_capacity, par = a.form.par, top_bits = a.form.top_bits;
+    const PoolStreams &ps = a.form.ps;
+    PoolPlan *pool = a.form.pool;
+    MsdPlan *msd = a.form.msd;
+    const unsigned long long xcc_map = a.form.setup.xcc_map;
+    const bool misplace = a.misplace;
+    const PoolPayloads *pv = a.form.pv;
     if (pv)
         VRS_LAUNCH(pool_pass_a_kernel<true>, dim3(8u * ps.tiles_per_stream), dim3(512), stream, ev, keys_in, keys_out, overflow, n, key_base, ps, pool, msd,
                    xcc_map, 0, overflow_capacity, par, *pv, top_bits);
@@ -869,9 +879,15 @@ hipError_t launch_pool_pass_a(hipStream_t stream, const uint32_t *keys_in, uint3
     return hipGetLastError();
 }
 
-hipError_t launch_pool_plan(hipStream_t stream, MsdPlan *msd, PoolPlan *pool, uint32_t n, uint32_t tiles_b_cap, uint32_t slack_capacity,
-                            const uint32_t *regions, const uint32_t *overflow, uint32_t key_base, const PoolStreams &ps, uint32_t sub_bits,
-                            uint32_t par, const PoolGroups *groups, bool keep_rooms, uint32_t top_bits) {
+hipError_t launch_pool_plan(hipStream_t stream, const PoolPlanArgs &a) {
+    MsdPlan *msd = a.form.msd;
+    PoolPlan *pool = a.form.pool;
+    const uint32_t n = a.form.n, key_base = a.form.key_base, par = a.form.par, top_bits = a.form.top_bits;
+    const uint32_t tiles_b_cap = a.tiles_b_cap, slack_capacity = a.slack_capacity, sub_bits = a.sub_bits;
+    const uint32_t *regions = a.regions, *overflow = a.overflow;
+    const PoolStreams &ps = a.form.ps;
+    const PoolGroups *groups = a.groups;
+    const bool keep_rooms = a.keep_rooms;
     if (ps.tiles_per_stream > kPoolMaxTilesA || tiles_b_cap > kPoolMaxTilesB || (groups && keep_rooms)) return hipErrorInvalidValue;
     const dim3 grid(256), block(512);
     const uint32_t keep = keep_rooms ? 1u : 0u;
@@ -888,10 +904,16 @@ hipError_t launch_pool_plan(hipStream_t stream, MsdPlan *msd, PoolPlan *pool, ui
     return hipGetLastError();
 }
 
-hipError_t launch_pool_pass_b(hipStream_t stream, const uint32_t *regions, const uint32_t *overflow, uint32_t *slack, uint32_t n, MsdPlan *msd,
-                              PoolPlan *pool, uint32_t tiles_b, uint32_t key_base, uint32_t local_cap, uint32_t slack_capacity,
-                              unsigned long long xcc_map, uint32_t stamp, uint32_t sub_bits, uint32_t par, LaunchEvents ev, bool grouped,
-                              const PoolPayloads *pv, uint32_t top_bits) {
+hipError_t launch_pool_pass_b(hipStream_t stream, const PoolPassBArgs &a, LaunchEvents ev) {
+    const uint32_t *regions = a.regions, *overflow = a.overflow;
+    uint32_t *slack = a.slack;
+    MsdPlan *msd = a.form.msd;
+    PoolPlan *pool = a.form.pool;
+    const uint32_t n = a.form.n, key_base = a.form.key_base, par = a.form.par, top_bits = a.form.top_bits;
+    const uint32_t tiles_b = a.tiles_b, local_cap = a.local_cap, slack_capacity = a.slack_capacity, stamp = a.stamp, sub_bits = a.sub_bits;
+    const unsigned long long xcc_map = a.form.setup.xcc_map;
+    const bool grouped = a.grouped;
+    const PoolPayloads *pv = a.form.pv;
     if (tiles_b == 0) return hipSuccess;
     if (tiles_b > kPoolMaxTilesB || stamp == 0u) return hipErrorInvalidValue;
     // (grouped keys lie in `regions` alone: no slot is an overflow slot)

@@ -252,10 +252,16 @@ __global__ __launch_bounds__(64, 4) void pool_local_sort_wave_kernel(const uint3
 
 }  // namespace
 
-hipError_t launch_pool_local_sort(hipStream_t stream, const uint32_t *slack, uint32_t *keys_out, uint32_t n, MsdPlan *msd, const PoolPlan *pool,
-                                  PoolShape shape, OnesweepPlanHead *dev_head, OnesweepPlanHead *host_head, uint32_t stamp, uint32_t par,
-                                  LaunchEvents ev, uint32_t top_bytes, uint32_t *host_log, bool retry, const PoolPayloads *pv) {
-    const uint32_t again = retry ? 1u : 0u;
+hipError_t launch_pool_local_sort(hipStream_t stream, const PoolLocalSortArgs &a, LaunchEvents ev) {
+    const uint32_t *slack = a.slack;
+    uint32_t *keys_out = a.keys_out, *host_log = a.host_log;
+    MsdPlan *msd = a.form.msd;
+    const PoolPlan *pool = a.form.pool;
+    const PoolShape shape = a.shape;
+    OnesweepPlanHead *dev_head = a.dev_head, *host_head = a.host_head;
+    const uint32_t n = a.form.n, stamp = a.stamp, par = a.form.par, top_bytes = a.top_bytes;
+    const PoolPayloads *pv = a.form.pv;
+    const uint32_t again = a.retry ? 1u : 0u;
     uint32_t *cursors = &msd->cursor_a[0][0];
     if (top_bytes == 0u || top_bytes > 256u || (top_bytes << shape.sub_bits) > kPoolMaxBuckets) return hipErrorInvalidValue;
     if (pv || shape.local >= 4u) {  // pairs

@@ -483,31 +483,30 @@ static void launch_digit_tables_variant(hipStream_t stream, const void *keys, ui
                fp, msd_counts, msd_counts ? msd_counts + kMsdBuckets : nullptr, msd_only, msd_base, msd_force_shift);
 }
 
-hipError_t launch_digit_tables_msd(hipStream_t stream, const void *keys, uint32_t n, uint32_t group_len, uint32_t *tables,
-                                   uint32_t *status, size_t status_words, int compute_units, uint32_t *msd_counts,
-                                   bool msd_only, LaunchEvents ev, uint32_t key_base, uint32_t force_shift) {
-    launch_digit_tables_variant<uint32_t, 8, 1024, 32, kDtUnroll, 4, true>(stream, keys, n, 0, group_len, tables, status,
-                                                                               status_words, compute_units, ev,
-                                                                               FusedPlanArgs{}, msd_counts, msd_only ? 1u : 0u, key_base, force_shift);
+hipError_t launch_digit_tables_msd(hipStream_t stream, const DigitTablesMsdArgs &a, LaunchEvents ev) {
+    launch_digit_tables_variant<uint32_t, 8, 1024, 32, kDtUnroll, 4, true>(stream, a.keys, a.n, 0, a.group_len, a.tables, a.status,
+                                                                               a.status_words, a.setup.compute_units, ev,
+                                                                               FusedPlanArgs{}, a.msd_counts, a.msd_only ? 1u : 0u, a.key_base, a.force_shift);
     return hipGetLastError();
 }
 
-hipError_t launch_digit_tables(hipStream_t stream, const void *keys, uint32_t n, int key_bytes, uint32_t base_shift,
-                               uint32_t group_len, uint32_t groups, uint32_t *tables, uint32_t *status,
-                               size_t status_words, int compute_units, LaunchEvents ev, const FusedPlan *fused) {
+hipError_t launch_digit_tables(hipStream_t stream, const DigitTablesArgs &a, LaunchEvents ev) {
+    const uint32_t groups = a.groups;
+    const int key_bytes = a.key_bytes;
     FusedPlanArgs fp{};
-    if (fused) {
-        fp.plan = fused->plan;
-        fp.host_head = fused->host_head;
-        fp.done = fused->done;
-        fp.stamp = fused->stamp;
-        fp.tile = fused->tile;
-        fp.tile_cap = fused->tile_cap;
-        fp.blind_cap = fused->blind_cap;
-        fp.cuts0 = fused->cuts0;
+    if (a.fused_plan) {
+        fp.plan = a.fused_plan;
+        fp.host_head = a.geo.host_head;
+        fp.done = a.fused_done;
+        fp.stamp = a.geo.stamp;
+        fp.tile = a.geo.tile;
+        fp.tile_cap = a.geo.tile_cap;
+        fp.blind_cap = a.geo.blind_cap;
+        fp.cuts0 = a.geo.cuts0;
     }
-#define VRS_DT(K, G, T, C, U, O) \
-    launch_digit_tables_variant<K, G, T, C, U, O>(stream, keys, n, base_shift, group_len, tables, status, status_words, compute_units, ev, fp)
+#define VRS_DT(K, G, T, C, U, O)                                                                                                      \
+    launch_digit_tables_variant<K, G, T, C, U, O>(stream, a.keys, a.geo.n, a.base_shift, a.geo.group_len, a.tables, a.status, a.status_words, \
+                                                  a.setup.compute_units, ev, fp)
     // (THREADS, COPIES, UNROLL, OCC): one 1024-thread workgroup per CU (32 groups: 131 KiB of LDS counters, 8 groups: 57)
     if (key_bytes == 8) {
         if (groups == 32) VRS_DT(uint64_t, 32, 1024, 32, kDtUnroll, 4);
@@ -536,9 +535,13 @@ StreamCuts pass0_stream_cuts(uint32_t n, uint32_t group_len, uint32_t groups) {
     return c;
 }
 
-hipError_t launch_plan(hipStream_t stream, uint32_t *tables, OnesweepPlan *plan, OnesweepPlanHead *host_head,
-                       uint32_t stamp, uint32_t n, uint32_t group_len, uint32_t groups, uint32_t tile, uint32_t tile_cap,
-                       uint32_t blind_cap, const StreamCuts &cuts0) {
+hipError_t launch_plan(hipStream_t stream, const PlanArgs &a) {
+    uint32_t *tables = a.tables;
+    OnesweepPlan *plan = a.plan;
+    const uint32_t groups = a.groups;
+    OnesweepPlanHead *host_head = a.geo.host_head;
+    const uint32_t stamp = a.geo.stamp, n = a.geo.n, group_len = a.geo.group_len, tile = a.geo.tile, tile_cap = a.geo.tile_cap, blind_cap = a.geo.blind_cap;
+    const StreamCuts &cuts0 = a.geo.cuts0;
     const dim3 grid(1), block(4 * kBins);
     if (groups == 32)
         hipLaunchKernelGGL(plan_kernel<32>, grid, block, 0, stream, tables, plan, host_head, stamp, n, group_len, tile, tile_cap, blind_cap, cuts0);
@@ -551,12 +554,18 @@ hipError_t launch_plan(hipStream_t stream, uint32_t *tables, OnesweepPlan *plan,
     return hipGetLastError();
 }
 
-hipError_t launch_onesweep_scatter(hipStream_t stream, const void *keys_in, void *keys_out, const uint32_t *values_in,
-                                   uint32_t *values_out, const OnesweepPlan *plan, uint32_t pass, uint32_t shift,
-                                   uint32_t *status, uint32_t grid_tiles, int forced, bool atomic_rank,
-                                   unsigned long long xcc_map, int key_bytes, uint32_t spin_budget, int hold_tile,
-                                   LaunchEvents ev, bool misplace, uint32_t key_base, MsdPlan *reserve, uint32_t *drift) {
-    const int mis = misplace ? 1 : 0, force = forced;
+hipError_t launch_onesweep_scatter(hipStream_t stream, const OnesweepScatterArgs &a, LaunchEvents ev) {
+    const void *keys_in = a.keys_in;
+    void *keys_out = a.keys_out;
+    const uint32_t *values_in = a.values_in;
+    uint32_t *values_out = a.values_out, *status = a.status, *drift = a.setup.drift;
+    const OnesweepPlan *plan = a.plan;
+    MsdPlan *reserve = a.reserve;
+    const uint32_t pass = a.pass, shift = a.shift, grid_tiles = a.grid_tiles, spin_budget = a.setup.spin_budget, key_base = a.key_base;
+    const int key_bytes = a.key_bytes, hold_tile = a.hold_tile;
+    const bool atomic_rank = a.setup.atomic_rank;
+    const unsigned long long xcc_map = a.setup.xcc_map;
+    const int mis = a.misplace ? 1 : 0, force = a.forced;
     if (grid_tiles == 0) return hipSuccess;
     const dim3 grid(kStreams * grid_tiles), block(64 * kLbWaves);
     const bool pairs = values_in != nullptr;

@@ -123,6 +123,20 @@ def test_every_dtype_side_and_width_in_every_tier(ctx, dtype):
         check(ctx, sorted_seq(dtype, 40001, rng), values(dtype, 70000, rng, nan=True), tier="table")
 
 
+@pytest.mark.parametrize("dtype", NARROW)
+def test_views_that_start_off_a_4_byte_boundary(ctx, dev, dtype):
+    """seq[1:] / x[1:] of a 1- or 2-byte dtype are contiguous but not 4-byte aligned, which vrs_buffer_wrap refuses: the drop-in raised
+    'device_ptr must be 4-byte aligned' (found by tools/fuzz_ops.py)"""
+    rng = np.random.default_rng(31)
+    seq, x = sorted_seq(dtype, 3001, rng), values(dtype, 2001, rng, nan=True)
+    seq_d, x_d = seq.to(dev), x.to(dev)
+    for by in (1, 2, 3):
+        for right in (False, True):
+            want = torch.searchsorted(seq[by:].contiguous(), x[by:].contiguous(), right=right)
+            assert torch.equal(vrs.searchsorted(seq_d[by:], x_d[by:], right=right).cpu(), want), (dtype, by, right)
+            assert torch.equal(vrs.bucketize(x_d[by:], seq_d[by:], right=right).cpu(), want), (dtype, by, right)
+
+
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16", "float32", "float64"])
 def test_sequences_that_end_in_nans_against_numpy(ctx, dtype):
     rng = np.random.default_rng(5)

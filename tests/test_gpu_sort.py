@@ -91,6 +91,18 @@ def test_device_torch_agrees_without_nan_or_zero(dtype, descending):
     check(x.to(DEV), descending=descending, device_ref=True)
 
 
+@pytest.mark.parametrize("dtype", [torch.int8, torch.uint8, torch.int16, torch.float16, torch.bfloat16], ids=str)
+def test_a_view_that_starts_off_a_4_byte_boundary(dtype):
+    """x[1:] of a 1- or 2-byte dtype is contiguous but not 4-byte aligned, which vrs_buffer_wrap refuses: the drop-in raised 'device_ptr
+    must be 4-byte aligned' (found by tools/fuzz_ops.py) where it documents any shape and strides"""
+    g = torch.Generator().manual_seed(13)
+    base = make(dtype, (4269,), g).to(DEV)
+    for by in (1, 2, 3):
+        assert base[by:].is_contiguous() and (base[by:].data_ptr() % 4 != 0 or by * base.element_size() % 4 == 0)
+        check(base[by:])
+        check(base[by:by + 4200].view(100, 42), dim=0, descending=True)
+
+
 def test_torch_order_of_specials():
     x = torch.tensor([1, float("nan"), -0.0, 0.0, -float("nan"), -1, 0.0, -0.0, float("inf"), -float("inf")], device=DEV)
     assert vrs.argsort(x).tolist() == [9, 5, 2, 3, 6, 7, 0, 8, 1, 4]

@@ -1,6 +1,7 @@
 """Randomised end-to-end check on the GPU: random N, B, key width, distribution, pairs, ranking method, against numpy.
 Every third case goes through the one-call sort with a random threshold (one counting read + look-back scatter
 passes above it), on a sub-range of a larger allocation at a random 4-byte alignment.
+The torch-level entry points (sort, topk, unique, searchsorted, ...) are fuzzed by tools/fuzz_ops.py.
    python tools/fuzz_gpu.py [seconds] [seed]"""
 import ctypes
 import sys

@@ -27,6 +27,12 @@ def row_offsets(rows: int, length: int, device):
     return ((bounds + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)
 
 
+def aligned(t):
+    """t, or a copy of it when its memory starts off a 4-byte boundary (vrs_buffer_wrap takes no other): a contiguous view of a 1- or
+    2-byte dtype that begins 1 to 3 bytes into its allocation, x[1:] of an int8 tensor."""
+    return t.clone() if t.data_ptr() % 4 else t
+
+
 @contextmanager
 def buffers(ctx, *tensors):
     """Buffers over the tensors' device memory (numel * element_size bytes each): yields their handles in order, None for a tensor that

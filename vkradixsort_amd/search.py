@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 
 from . import capi
-from ._torch import buffers, context_for
+from ._torch import aligned, buffers, context_for
 from .capi import VrsError
 from .sort import _dtype_code
 
@@ -40,7 +40,7 @@ def searchsorted(sorted_sequence, input, *, out_int32: bool = False, right: bool
     Shapes as torch: a 1-D sequence with an input of any shape (a Python number too), or a sequence and an input that differ in
     their last dimension only.  `sorter`: int64 indices of the sequence's shape that sort it along its last dimension.  An input of
     another dtype (or a number) is promoted with the sequence as torch does (torch.result_type, then .to()); non-contiguous tensors
-    are made contiguous first (one copy).  Refusals are VrsError and come before any device work."""
+    and 1- or 2-byte views that start off a 4-byte boundary are made contiguous and aligned first (one copy).  Refusals are VrsError and come before any device work."""
     import torch
 
     if not isinstance(sorted_sequence, torch.Tensor):
@@ -77,7 +77,7 @@ def searchsorted(sorted_sequence, input, *, out_int32: bool = False, right: bool
     if seq.numel() >= 1 << 32 or (not scalar and input.numel() >= 1 << 32):
         _refuse("searchsorted takes fewer than 2^32 elements on either side")
     values = torch.tensor(input, dtype=common, device=device) if scalar else input
-    seq_c, values_c = seq.to(common).contiguous(), values.to(common).contiguous()
+    seq_c, values_c = aligned(seq.to(common).contiguous()), aligned(values.to(common).contiguous())
     sorter_c = sorter.contiguous() if sorter is not None else None
     out = torch.empty(values_c.shape, dtype=torch.int32 if out_int32 else torch.int64, device=device)
     nq, nb = values_c.numel(), seq_c.numel()

@@ -7,7 +7,7 @@ writes the values back from the sorted ranks and the int64 indices from the posi
 from __future__ import annotations
 
 from . import capi
-from ._torch import buffers, context_for, row_offsets
+from ._torch import aligned, buffers, context_for, row_offsets
 from .capi import VrsError
 
 
@@ -38,7 +38,7 @@ def _run(x, dim: int, descending: bool, want_values: bool, want_indices: bool):
     if x.dim() == 0 or n == 0:  # (as torch: a 0-d tensor is its own sort, its index 0)
         return (x.clone() if want_values else None), (torch.zeros(x.shape, dtype=torch.int64, device=device) if want_indices else None)
     dim %= x.dim()
-    xt = x.movedim(dim, -1).contiguous()  # (a contiguous tensor sorted along its last dim is not copied)
+    xt = aligned(x.movedim(dim, -1).contiguous())  # (a contiguous tensor sorted along its last dim is not copied, unless off a 4-byte boundary)
     L = xt.shape[-1]
     rows = n // L
     is_float = x.dtype.is_floating_point

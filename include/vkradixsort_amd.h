@@ -464,6 +464,62 @@ int vrs_search_plan(vrs_context ctx, uint32_t num_boundaries, uint32_t boundary_
 int vrs_search_stats(vrs_context ctx, uint64_t *lds_calls, uint64_t *table_calls, uint64_t *direct_calls, uint64_t *indexed_calls);
 
 /*
+ * Counting (build extension; no reference counterpart): torch.bincount / torch.histc, and the count behind torch.histogram.
+ * `values`: num_values elements of `dtype` (a vrs_sort_dtype).  `mode` says how an element x becomes a bin in [0, num_bins):
+ *   VRS_BIN_INDEX   uint8, int8, int16, int32 or int64 elements: the element is the bin.  x < 0 and x >= num_bins have none.
+ *   VRS_BIN_LINEAR  float16, bfloat16, float32 or float64 elements and a finite range lo < hi:
+ *                       bin = (int)((x - lo) * num_bins / (hi - lo)),   bin == num_bins becomes num_bins - 1
+ *                   in float32 (float64 elements: in float64; 16-bit elements are widened to float32 first; lo, hi and num_bins are
+ *                   converted to that type), the three operations in this order, each rounded on its own -- torch.histc's rule,
+ *                   and the definition of this mode (vrs_bin_linear_host evaluates the same function on the host).  x < lo, x > hi
+ *                   and NaN have none.
+ * Every element that has a bin adds 1 to it, or, with weight_dtype = VRS_SORT_FLOAT32 / VRS_SORT_FLOAT64 (otherwise
+ * VRS_BIN_NO_WEIGHTS), its weight: `weights` holds num_values of them.  `out` takes num_bins results of out_dtype:
+ *   counts        int64, or float16 / bfloat16 / float32 / float64.  Counts are accumulated as 32-bit integers (a call takes fewer
+ *                 than 2^32 elements) and converted once: a float result is the correctly rounded count, where a sum of float ones
+ *                 stops growing at 2^24 in float32 (as torch.histc's does).
+ *   weighted sums out_dtype = weight_dtype; summed in that type by float atomics, in no specified order (as torch).
+ * `skipped`: NULL, or two uint64 that receive the number of elements below the range (x < 0; x < lo) and at or beyond its end
+ * (x >= num_bins; x > hi).  NaN counts in neither.
+ * The library clears what it accumulates into (on the context's stream): `out` for int64 counts and weighted sums, otherwise 32-bit
+ * counters in `scratch`, which a finish kernel converts.  scratch: at least the bytes vrs_bin_count_plan / vrs_bin_count_scratch_bytes
+ * report (never 0: the two skip counters live there); contents on entry and afterwards unspecified.  values and weights are never
+ * written, nor are bytes of `out` past num_bins entries.  num_values == 0: every output 0.
+ * Tiers (vrs_bincount_tier, decided by vrs_bin_count_tier_for): counters of num_bins x 4 bytes (8 with float64 weights) that fit
+ * VRS_TUNE_BINCOUNT_LDS_BYTES are kept in every workgroup's LDS and flushed once, the non-zero ones only; otherwise every add is a
+ * global atomic.  In both a wave whose elements all fall into one bin adds once.
+ * A NULL context, out or scratch (values / weights when there are elements), a dtype outside the mode's list, an unknown mode,
+ * num_bins == 0, a range that is not finite, not lo < hi or whose width hi - lo overflows the type the rule is evaluated in (linear
+ * mode; lo = -3e38, hi = 3e38 in float32), a weight dtype other than the two, an out dtype outside the list above and undersized
+ * buffers (out: num_bins entries; values, weights: num_values; skipped: 16 bytes; scratch: what the plan reports):
+ * VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Stream-ordered on the context's stream;
+ * the call only enqueues (after settling a pending one-call sort) and never waits for the device.
+ */
+enum { VRS_BIN_INDEX = 0, VRS_BIN_LINEAR = 1 }; /* mode */
+enum { VRS_BIN_NO_WEIGHTS = -1 };               /* weight_dtype of a count */
+typedef enum vrs_bincount_tier {
+    VRS_BINCOUNT_LDS = 0,   /* the counters fit VRS_TUNE_BINCOUNT_LDS_BYTES */
+    VRS_BINCOUNT_GLOBAL = 1 /* every larger num_bins */
+} vrs_bincount_tier;
+int vrs_bin_count(vrs_context ctx, vrs_buffer values, uint32_t num_values, int dtype, int mode, double lo, double hi, uint32_t num_bins,
+                  vrs_buffer weights /* NULL without weights */, int weight_dtype, int out_dtype, vrs_buffer out,
+                  vrs_buffer skipped /* may be NULL */, vrs_buffer scratch);
+/* the classification both the device and the tests use: a pure function, needs no device.  counter_bytes: 4, or 8 for float64
+ * weights; lds_bytes: the value of VRS_TUNE_BINCOUNT_LDS_BYTES (0 = never the LDS tier; clamped to 163840).  *tier = VRS_BINCOUNT_*. */
+int vrs_bin_count_tier_for(uint32_t num_bins, uint32_t counter_bytes, uint32_t lds_bytes, int *tier);
+/* the scratch a call needs: a pure function, needs no device.  256 bytes, and 4 bytes per bin (rounded up to 256) more for counts
+ * whose out dtype is not int64.  Refuses what vrs_bin_count refuses about num_bins and the two dtypes. */
+int vrs_bin_count_scratch_bytes(uint32_t num_bins, int weight_dtype, int out_dtype, uint64_t *bytes);
+/* the tier vrs_bin_count will take on this context (its tuning as it stands) and the scratch it needs; no device work */
+int vrs_bin_count_plan(vrs_context ctx, uint32_t num_bins, int weight_dtype, int out_dtype, int *tier, uint64_t *scratch_bytes);
+/* cumulative per context: calls each tier ran (calls without elements run none).  Counted on the host: does not wait for the stream.
+ * Either pointer may be NULL. */
+int vrs_bin_count_stats(vrs_context ctx, uint64_t *lds_calls, uint64_t *global_calls);
+/* VRS_BIN_LINEAR's rule on the host, by the function the kernels compile: bins[i] = the bin of element i of `values` (host memory,
+ * num_values elements of a float dtype), or -1 when it has none.  Needs no device. */
+int vrs_bin_linear_host(const void *values, uint64_t num_values, int dtype, double lo, double hi, uint32_t num_bins, int64_t *bins);
+
+/*
  * Run-length encoding (build extension; no reference counterpart -- the reference's callers find each cell's or tile's [start, end)
  * in the sorted ids themselves): n keys of key_bytes (4 or 8) each, in any order, as maximal runs of bit-identical consecutive keys
  * (torch.unique_consecutive).  With R runs: out_keys[j] = the key of run j, out_offsets[j] = its first position and out_offsets[R] = n,
@@ -843,6 +899,9 @@ typedef enum vrs_tuning_key {
                                        0 = never.  Default 65536 */
     VRS_TUNE_SEARCH_INDEX_MIN_QUERIES = 31, /* sorted-sequence search, rows beyond the LDS tier: from this many queries per boundary row on the call
                                        builds the sampled index first.  0 = never (plain lower / upper bound).  Default 65536 */
+    VRS_TUNE_BINCOUNT_LDS_BYTES = 32, /* counting (vrs_bin_count): a call whose counters (num_bins x 4 bytes; x 8 with float64 weights) take up to this
+                                       many bytes counts in every workgroup's LDS and flushes once; 0 = never.  0 .. 163840.  Default 65536 (two
+                                       workgroups per CU): a first setting, not a measured one (DESIGN "K11") */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

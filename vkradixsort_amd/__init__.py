@@ -7,9 +7,12 @@ segmented  many independent segments sorted in one call (sort_segments over Buff
 topk       the k smallest / largest keys of every segment by radix select (topk_segments over Buffers, topk for torch tensors)
 sort       torch.sort / torch.argsort drop-ins: any dim, descending, nine dtypes, torch's order bit for bit (sort, sort_values, argsort)
 search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize)
+binning    torch.bincount / torch.histc / torch.histogram drop-ins: counters in LDS or global memory, integer counts converted once
+           (bincount, histc, histogram)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
            for torch tensors)
 """
+from .binning import bincount, bincount_stats, histc, histogram  # noqa: F401
 from .capi import PushConstants, VrsError, load_library  # noqa: F401
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)

@@ -103,6 +103,14 @@ VRS_TUNE_SEARCH_LDS_BYTES, VRS_TUNE_SEARCH_TABLE_MIN_QUERIES, VRS_TUNE_SEARCH_IN
 SEARCH_LDS_BYTES_DEFAULT, SEARCH_LDS_BYTES_MAX = 64 * 1024, 160 * 1024
 SEARCH_TABLE_MIN_QUERIES_DEFAULT, SEARCH_INDEX_MIN_QUERIES_DEFAULT = 1 << 16, 1 << 16
 SEARCH_LINE_BYTES = 128  # boundaries one index entry stands for
+# counting (vrs_bin_count): modes, tiers (vrs_bincount_tier), the tuning key and the library's default for it, the launch's shape
+VRS_BIN_INDEX, VRS_BIN_LINEAR = 0, 1
+VRS_BIN_NO_WEIGHTS = -1
+VRS_BINCOUNT_LDS, VRS_BINCOUNT_GLOBAL = 0, 1
+VRS_TUNE_BINCOUNT_LDS_BYTES = 32
+BINCOUNT_LDS_BYTES_DEFAULT, BINCOUNT_LDS_BYTES_MAX = 64 * 1024, 160 * 1024
+BINCOUNT_TILE_BYTES = 16 * 1024  # of elements, per workgroup and step of its loop
+BINCOUNT_WORKGROUPS_PER_CU = 2   # one when a workgroup's counters take more than half of BINCOUNT_LDS_BYTES_MAX
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -245,6 +253,13 @@ _SIGNATURES = [
     ("vrs_search_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, c_int, c_int, POINTER(c_uint64)]),
     ("vrs_search_plan", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
     ("vrs_search_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_bin_count", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_int, c_double, c_double, c_uint32, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p]),
+    ("vrs_bin_count_tier_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
+    ("vrs_bin_count_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
+    ("vrs_bin_count_plan", c_int, [c_void_p, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
+    ("vrs_bin_count_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_bin_linear_host", c_int, [c_void_p, c_uint64, c_int, c_double, c_double, c_uint32, c_void_p]),
     ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
     ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

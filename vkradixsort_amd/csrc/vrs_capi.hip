@@ -703,6 +703,10 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
             if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the search's index threshold must be >= 0");
             ctx->search_index_min_queries = static_cast<uint32_t>(value);
             return VRS_OK;
+        case VRS_TUNE_BINCOUNT_LDS_BYTES:
+            if (value < 0 || value > 160 * 1024) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the counting kernels' LDS capacity must be 0 .. 163840 bytes");
+            ctx->bincount_lds_bytes = static_cast<uint32_t>(value);
+            return VRS_OK;
         case VRS_TUNE_MSD_POOL_PAIRS_PACKED:
             if (value < -1 || value > 1) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pairs' packed local sort: -1 (by size), 0 (never) or 1 (always)");
             ctx->os_pool_pairs_packed = value;

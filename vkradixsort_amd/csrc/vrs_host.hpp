@@ -176,6 +176,9 @@ struct vrs_context_t {
     uint32_t search_table_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_TABLE_MIN_QUERIES
     uint32_t search_index_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_INDEX_MIN_QUERIES
     uint64_t search_calls[4] = {};                // calls per tier (vrs_search_stats)
+    // counting (vrs_capi_bincount.hip); the default is vrs_bincount.hpp's kBinCountDefaultLdsBytes
+    uint32_t bincount_lds_bytes = 64u * 1024u;    // VRS_TUNE_BINCOUNT_LDS_BYTES
+    uint64_t bincount_calls[2] = {};              // calls per tier (vrs_bin_count_stats)
 };
 
 struct vrs_buffer_t {

@@ -410,6 +410,65 @@ int vrs_topk_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, uint3
 int vrs_topk_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments);
 
 /*
+ * One-rank selection (build extension; no reference counterpart): torch.kthvalue / torch.median / torch.nanmedian -- one entry of every
+ * segment's sorted order, its own bits and where it sat, by radix select, in one call.  src: num_elements elements of `dtype` (a
+ * vrs_sort_dtype); offsets: a device buffer of num_segments + 1 uint32; segment i is src[offsets[i], offsets[i+1]) clamped exactly as
+ * vrs_segment_tier_for clamps it, L its length.  r is the rank vrs_sort_rank_keys gives (unsigned as is; signed with the sign bit
+ * flipped; floats by value with -0.0 == +0.0 and every NaN the largest); VRS_SELECT_DESCENDING ranks by the complement of r.  The map is
+ * applied in registers as the elements are read, element by element (a segment may begin at any element offset); src and offsets are
+ * never written.
+ * The call answers entry j (0-based) of the segment's STABLE ascending order of r -- the element sort(..., stable=True) puts at
+ * position j: out_values[i] gets that element's own bits, read from src (a NaN's payload and a zero's sign are kept), out_indices[i]
+ * (may be NULL) its position relative to the clamped begin as uint32.  A segment without such a j (L == 0; VRS_SELECT_KTH with k > L)
+ * gets index 0xFFFFFFFF and all-zero value bits.  With nans = the segment's keys of the NaN class (0 for integer dtypes), counted by the
+ * first read, `mode` (vrs_select_mode) fixes j -- the rule is vrs_select_target_for's:
+ *   VRS_SELECT_KTH        j = k - 1 (1 <= k)
+ *   VRS_SELECT_MEDIAN     j = (L - 1) / 2 when nans == 0, else the first NaN of the stable order (L - nans ascending, 0 descending):
+ *                         torch's rule, a row with any NaN has median NaN
+ *   VRS_SELECT_NANMEDIAN  j = (L - nans - 1) / 2 among the non-NaN keys when nans < L (they follow the NaNs when descending), else the
+ *                         first NaN
+ * scratch: at least vrs_select_scratch_bytes(...) bytes, contents afterwards unspecified; given that much the call never fails for
+ * lack of memory.  num_segments == 0: VRS_OK, nothing done.  An unknown dtype, mode or flag bit, k == 0 with VRS_SELECT_KTH, a NULL
+ * context, src, offsets, out_values or scratch, undersized buffers (src: num_elements elements; out_values: num_segments elements;
+ * out_indices: num_segments uint32) and 8-byte elements off an 8-byte boundary: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
+ * Digits of at most 11 bits from the top of the dtype's 8 / 16 / 32 / 64 bits (1 / 2 / 3 / 6 levels); a segment is done once the
+ * chosen bin holds one key.  Tiers by clamped length (vrs_select_tier, decided by vrs_select_tier_for): ranks that fit 32 KB (8192 keys
+ * of up to 4 bytes, 4096 of 8) are read once into the LDS of one workgroup; longer segments are streamed by one workgroup each, one read
+ * per level; from VRS_TUNE_SELECT_GRID_MIN_KEYS on every phase is one launch over all the grid tier's segments, and after a level whose
+ * chosen bin holds at most L / VRS_TUNE_SELECT_COMPACT_DIVISOR keys, with two levels or more still to come (the copy costs one read of
+ * the segment, as a level does), the ranks of those keys are copied once into the scratch buffer (1024 ranks per 16384 keys of the
+ * segment: a bin beyond that is not copied, whatever the divisor), where the later levels read them.
+ * The index is found by counting the keys that match the final prefix in index order; nothing is emitted or sorted.
+ * Stream-ordered on the context's stream; the call only enqueues (after settling a pending one-call sort) and never waits for the device.
+ */
+typedef enum vrs_select_mode { VRS_SELECT_KTH = 0, VRS_SELECT_MEDIAN = 1, VRS_SELECT_NANMEDIAN = 2 } vrs_select_mode;
+enum { VRS_SELECT_DESCENDING = 1 }; /* flags */
+typedef enum vrs_select_tier {
+    VRS_SELECT_LDS = 0,   /* ranks of up to 32 KB (empty segments included) */
+    VRS_SELECT_BLOCK = 1, /* longer, below VRS_TUNE_SELECT_GRID_MIN_KEYS */
+    VRS_SELECT_GRID = 2   /* from VRS_TUNE_SELECT_GRID_MIN_KEYS on */
+} vrs_select_tier;
+int vrs_select_segments(vrs_context ctx, vrs_buffer src, uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments,
+                        int dtype /* vrs_sort_dtype */, int mode, uint32_t k, int flags, vrs_buffer out_values,
+                        vrs_buffer out_indices /* may be NULL */, vrs_buffer scratch);
+/* the scratch vrs_select_segments needs: a pure function, needs no device.  0 for num_segments == 0; with w = the bytes of the dtype's
+ * rank (vrs_sort_rank_bytes) at most num_elements * w / 16 + 4 * num_elements + 4 * num_segments + 1 MiB; never shrinks as
+ * num_elements grows. */
+int vrs_select_scratch_bytes(uint32_t num_elements, uint32_t num_segments, int dtype, uint64_t *bytes);
+/* the classification both the device and the tests use: a pure function, needs no device.  grid_min_keys: the value of
+ * VRS_TUNE_SELECT_GRID_MIN_KEYS (0 = never the grid tier); *tier = VRS_SELECT_*. */
+int vrs_select_tier_for(uint32_t begin, uint32_t end, uint32_t num_elements, int dtype, uint32_t grid_min_keys,
+                        uint32_t *clamped_begin, uint32_t *clamped_end, int *tier);
+/* the rule both the device and the tests use for the entry a mode asks for: a pure function, needs no device.  *valid = 0: the segment
+ * has no such entry (*j = 0).  Refuses an unknown mode and nans > len. */
+int vrs_select_target_for(int mode, uint32_t k, uint32_t len, uint32_t nans, int descending, uint32_t *j, int *valid);
+/* cumulative per context: segments each tier was given by the classification, and grid-tier segments that compacted (waits for the
+ * context's stream; any pointer may be NULL).  Grid-tier segments beyond the scratch buffer's slots -- num_elements / 8193, 4096 at the
+ * most -- count as grid and run in the BLOCK kernel. */
+int vrs_select_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments,
+                     uint64_t *compacted_segments);
+
+/*
  * Sorted-sequence search (build extension; no reference counterpart): torch.searchsorted / torch.bucketize / numpy.searchsorted.
  * `boundaries`: num_boundaries elements of `dtype` (a vrs_sort_dtype) as rows of boundary_row_len, each ascending in r; `queries`:
  * num_queries elements of the same dtype as rows of query_row_len.  Either there is exactly one boundary row, which every query
@@ -902,6 +961,12 @@ typedef enum vrs_tuning_key {
     VRS_TUNE_BINCOUNT_LDS_BYTES = 32, /* counting (vrs_bin_count): a call whose counters (num_bins x 4 bytes; x 8 with float64 weights) take up to this
                                        many bytes counts in every workgroup's LDS and flushes once; 0 = never.  0 .. 163840.  Default 65536 (two
                                        workgroups per CU): a first setting, not a measured one (DESIGN "K11") */
+    VRS_TUNE_SELECT_GRID_MIN_KEYS = 33, /* one-rank selection: segments of this many keys or more take the grid tier (every phase one launch
+                                         over all of them); 0 = never.  Default 2^17: top-k's measured crossover for the same walk shape,
+                                         a first setting, not measured for this kernel (DESIGN "K12") */
+    VRS_TUNE_SELECT_COMPACT_DIVISOR = 34, /* one-rank selection, grid tier: after a level whose chosen bin holds at most length / value keys
+                                         (and at most 1024 per 16384 keys of the segment, what its area holds) the matching keys' ranks are
+                                         copied once and the later levels read the copy; 0 = never.  Default 16, not measured (DESIGN "K12") */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

@@ -5,6 +5,8 @@ host/    C++ mirror of the reference's host classes (engine::GPUContext, Buffer,
 engine   the same interface for Python callers (tests, bench.py), a thin ctypes layer over the C ABI
 segmented  many independent segments sorted in one call (sort_segments over Buffers, sort_rows for 2-D torch tensors)
 topk       the k smallest / largest keys of every segment by radix select (topk_segments over Buffers, topk for torch tensors)
+selection  torch.kthvalue / torch.median / torch.nanmedian drop-ins by a one-rank radix select: nine dtypes, any dim (select_segments over
+           Buffers; kthvalue, median, nanmedian for torch tensors)
 sort       torch.sort / torch.argsort drop-ins: any dim, descending, nine dtypes, torch's order bit for bit (sort, sort_values, argsort)
 search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize)
 binning    torch.bincount / torch.histc / torch.histogram drop-ins: counters in LDS or global memory, integer counts converted once
@@ -18,6 +20,7 @@ from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, 
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
 from .search import bucketize, search_stats, searchsorted  # noqa: F401
 from .segmented import segmented_stats, sort_rows, sort_segments  # noqa: F401
+from .selection import kthvalue, median, nanmedian, select_scratch_bytes, select_segments, select_stats  # noqa: F401
 from .sort import argsort, sort, sort_values  # noqa: F401
 from .topk import topk, topk_segments, topk_stats  # noqa: F401
 from .unique import run_length_encode, unique, unique_consecutive, unique_keys  # noqa: F401

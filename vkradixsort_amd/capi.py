@@ -87,6 +87,13 @@ VRS_TOPK_LARGEST, VRS_TOPK_SORTED = 1, 2
 VRS_TOPK_LDS, VRS_TOPK_BLOCK, VRS_TOPK_GRID = 0, 1, 2
 TOPK_LDS_MAX = 8192
 TOPK_SORT_IN_LDS_MAX_K = 4096  # VRS_TOPK_SORTED beyond this k sorts the survivors with vrs_sort_segments_pairs_u32
+# one-rank selection (vrs_select_segments): modes, the flag, tiers (vrs_select_tier), the LDS tier's bytes of ranks, tuning keys and defaults
+VRS_SELECT_KTH, VRS_SELECT_MEDIAN, VRS_SELECT_NANMEDIAN = 0, 1, 2
+VRS_SELECT_DESCENDING = 1
+VRS_SELECT_LDS, VRS_SELECT_BLOCK, VRS_SELECT_GRID = 0, 1, 2
+SELECT_LDS_BYTES = 32 * 1024
+VRS_TUNE_SELECT_GRID_MIN_KEYS, VRS_TUNE_SELECT_COMPACT_DIVISOR = 33, 34
+SELECT_GRID_MIN_KEYS_DEFAULT, SELECT_COMPACT_DIVISOR_DEFAULT = 1 << 17, 16
 # run-length encoding and unique: scratch flags, key types, and the encode's tile (keys per look-back status word)
 VRS_RLE_COUNTS = 1
 VRS_UNIQUE_U32, VRS_UNIQUE_I32, VRS_UNIQUE_F32, VRS_UNIQUE_U64, VRS_UNIQUE_I64, VRS_UNIQUE_F64 = 0, 1, 2, 3, 4, 5
@@ -248,6 +255,11 @@ _SIGNATURES = [
     ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
     ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
     ("vrs_topk_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_select_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, c_int, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vrs_select_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+    ("vrs_select_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
+    ("vrs_select_target_for", c_int, [c_int, c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_int)]),
+    ("vrs_select_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_search_sorted", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("vrs_search_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
     ("vrs_search_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, c_int, c_int, POINTER(c_uint64)]),

@@ -280,6 +280,7 @@ int vrs_context_destroy(vrs_context ctx) {
     if (ctx->os_plan_a) (void)hipFree(ctx->os_plan_a);
     segmented_release(ctx);
     topk_release(ctx);
+    select_release(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return VRS_OK;
@@ -690,6 +691,14 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
         case VRS_TUNE_TOPK_GRID_MIN_KEYS:
             if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the top-k grid tier's threshold must be >= 0");
             ctx->topk_grid_min_keys = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_SELECT_GRID_MIN_KEYS:
+            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the selection's grid tier threshold must be >= 0");
+            ctx->select_grid_min_keys = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_SELECT_COMPACT_DIVISOR:
+            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the selection's compaction divisor must be >= 0");
+            ctx->select_compact_divisor = static_cast<uint32_t>(value);
             return VRS_OK;
         case VRS_TUNE_SEARCH_LDS_BYTES:
             if (value < 0 || value > 160 * 1024) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the search's LDS capacity must be 0 .. 163840 bytes");

@@ -25,6 +25,7 @@
 
 struct vrs_segmented_state;  // vrs_capi_segmented.hip
 struct vrs_topk_state;       // vrs_capi_topk.hip
+struct vrs_select_state;     // vrs_capi_select.hip
 
 struct vrs_context_t {
     int device = 0;
@@ -171,6 +172,10 @@ struct vrs_context_t {
     // top-k selection (vrs_capi_topk.hip)
     vrs_topk_state *topk = nullptr;
     uint32_t topk_grid_min_keys = 1u << 17;  // VRS_TUNE_TOPK_GRID_MIN_KEYS (vrs::kTopkDefaultGridMinKeys)
+    // one-rank selection (vrs_capi_select.hip); the defaults are vrs_select.hpp's kSelDefault*
+    vrs_select_state *select = nullptr;
+    uint32_t select_grid_min_keys = 1u << 17;  // VRS_TUNE_SELECT_GRID_MIN_KEYS
+    uint32_t select_compact_divisor = 16u;     // VRS_TUNE_SELECT_COMPACT_DIVISOR
     // sorted-sequence search (vrs_capi_search.hip); the defaults are vrs_search.hpp's kSearchDefault*
     uint32_t search_lds_bytes = 64u * 1024u;      // VRS_TUNE_SEARCH_LDS_BYTES
     uint32_t search_table_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_TABLE_MIN_QUERIES
@@ -313,6 +318,7 @@ int one_read_settle(vrs_context ctx);
 int settle_pending(vrs_context ctx);
 void segmented_release(vrs_context ctx);
 void topk_release(vrs_context ctx);
+void select_release(vrs_context ctx);
 
 // A context's cumulative device counters (count entries of T): made and zeroed on its stream at first use; read back once the calls
 // before have finished (all zeros when they were never made: counters == NULL).

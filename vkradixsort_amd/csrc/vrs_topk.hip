@@ -16,23 +16,13 @@
 #include "vrs_topk.hpp"
 
 #include "vrs_local_sort.hpp"
+#include "vrs_radix_select.hpp"  // hist_add, select_digit, grid_slots, grid_tiles, find_slot
 
 namespace vrs {
 namespace {
 
 __device__ __forceinline__ bool sel_less(uint32_t r, const TopkSel &s) { return s.shift < 32u && (r >> s.shift) < (s.prefix >> s.shift); }
 __device__ __forceinline__ bool sel_match(uint32_t r, const TopkSel &s) { return s.shift >= 32u || (r >> s.shift) == (s.prefix >> s.shift); }
-
-// counts digit d of the calling lane; one add for the whole instruction when every active lane has the same digit (equal keys)
-__device__ __forceinline__ void hist_add(uint32_t *s_hist, uint32_t d) {
-    const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
-    const uint64_t active = __ballot(1);
-    if (__ballot(d == d0) == active) {
-        if (count_below(active) == 0u) atomicAdd(&s_hist[d0], static_cast<uint32_t>(__popcll(active)));
-    } else {
-        atomicAdd(&s_hist[d], 1u);
-    }
-}
 
 // the digit histogram (level `level`) of the keys of one tile that match the selection so far; position p of the tile: load(p)
 template <int THREADS, int ITEMS, class Load>
@@ -49,44 +39,6 @@ __device__ __forceinline__ void hist_tile(Load load, uint32_t cnt, const TopkSel
         const uint32_t p = i * THREADS + threadIdx.x;
         if (p < cnt && sel_match(r[i], sel)) hist_add(s_hist, (r[i] >> shift) & mask);
     }
-}
-
-// Picks the digit that holds the need-th matching key (1 <= need <= keys counted): s_res = {d*, keys below it, keys at it}.
-template <int THREADS>
-__device__ __forceinline__ void select_digit(const uint32_t *s_hist, uint32_t need, uint32_t *s_wtot, uint32_t *s_res) {
-    constexpr int PER = kTopkBins / THREADS, WAVES = THREADS / 64;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t c[PER], sum = 0;
-#pragma unroll
-    for (int p = 0; p < PER; ++p) {
-        c[p] = s_hist[tid * PER + p];
-        sum += c[p];
-    }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= static_cast<uint32_t>(o)) incl += t;
-    }
-    if (lane == 63u) s_wtot[wave] = incl;
-    __syncthreads();
-    uint32_t excl = incl - sum;
-#pragma unroll
-    for (int v = 0; v < WAVES; ++v) excl += static_cast<uint32_t>(v) < wave ? s_wtot[v] : 0u;
-    if (excl < need && need <= excl + sum) {  // exactly one thread
-        uint32_t acc = excl;
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            if (acc + c[p] >= need) {
-                s_res[0] = tid * PER + p;
-                s_res[1] = acc;
-                s_res[2] = c[p];
-                break;
-            }
-            acc += c[p];
-        }
-    }
-    __syncthreads();
 }
 
 __device__ __forceinline__ void sel_apply(TopkSel &sel, int level, uint32_t d, uint32_t below, uint32_t at) {
@@ -287,24 +239,6 @@ __global__ __launch_bounds__(THREADS) void topk_workgroup_kernel(TopkArgs a, con
 // ---- GRID tier: kernels that walk the virtual tiles [0, tiles taken) of every slot ----
 constexpr int kGridThreads = 1024, kGridItems = 16;
 static_assert(kGridThreads * kGridItems == static_cast<int>(kTopkTile), "a grid tile is one pass of a workgroup");
-
-__device__ __forceinline__ uint32_t grid_slots(const TopkControl *ctl, uint32_t slot_cap) {
-    return min(static_cast<uint32_t>(ctl->grid_packed), slot_cap);
-}
-__device__ __forceinline__ uint32_t grid_tiles(const TopkControl *ctl, uint32_t slot_cap, uint32_t tile_cap) {
-    const uint32_t ns = grid_slots(ctl, slot_cap);
-    return ns == 0u ? 0u : min(static_cast<uint32_t>(ctl->grid_packed >> 32), tile_cap);
-}
-// the slot whose tiles hold virtual tile t: the last slot with tile_base <= t (tile bases grow with the slot)
-__device__ __forceinline__ uint32_t find_slot(const TopkSlot *slots, uint32_t ns, uint32_t t) {
-    uint32_t lo = 0, hi = ns;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) / 2u;
-        if (slots[mid].tile_base <= t) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void topk_grid_init_kernel(const TopkControl *__restrict__ ctl, uint32_t *__restrict__ hist, uint32_t slot_cap) {
     const uint32_t ns = grid_slots(ctl, slot_cap);

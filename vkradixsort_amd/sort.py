@@ -11,12 +11,12 @@ from ._torch import aligned, buffers, context_for, row_offsets
 from .capi import VrsError
 
 
-def _dtype_code(torch, dtype):
+def _dtype_code(torch, dtype, name: str = "sort"):
     codes = {torch.int8: capi.VRS_SORT_INT8, torch.uint8: capi.VRS_SORT_UINT8, torch.int16: capi.VRS_SORT_INT16,
              torch.int32: capi.VRS_SORT_INT32, torch.int64: capi.VRS_SORT_INT64, torch.float16: capi.VRS_SORT_FLOAT16,
              torch.bfloat16: capi.VRS_SORT_BFLOAT16, torch.float32: capi.VRS_SORT_FLOAT32, torch.float64: capi.VRS_SORT_FLOAT64}
     if dtype not in codes:
-        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, f"sort takes int8, uint8, int16, int32, int64, float16, bfloat16, float32 or "
+        raise VrsError(capi.VRS_ERROR_INVALID_ARGUMENT, f"{name} takes int8, uint8, int16, int32, int64, float16, bfloat16, float32 or "
                                                         f"float64, not {dtype}")
     return codes[dtype]
 

@@ -361,6 +361,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void scatter_kernel(const K *__res
     using DG = typename std::conditional<SPLIT, SplitDigit<K>, RadixDigit<K>>::type;
     __shared__ ChunkSmem<K, ITEMS, WAVES, PAIRS> sm;
     __shared__ K s_split[SPLIT ? 256 : 1];
+    VRS_MARK(6);
     DG dg;
     if constexpr (SPLIT) {
         stage_splitters(s_split, splitters, num_splitters);

@@ -20,9 +20,11 @@
     } while (0)
 
 // Phase-timing hooks for tools/lab (compiled out of the product library).
+// (marks 0 .. 5: scatter_chunk's phases; 6: kernel entry; VRS_MARK_FLUSH(k): kernel k's marks go out -- 0, or none given: the
+// contract scatter, 1 / 2: the pool form's passes)
 #ifndef VRS_MARK
 #define VRS_MARK(i)
-#define VRS_MARK_FLUSH()
+#define VRS_MARK_FLUSH(...)
 #endif
 namespace vrs {
 
@@ -402,6 +404,46 @@ __device__ __forceinline__ void recount_keys(uint32_t *cnt, const K *keys, uint3
     for (uint32_t j = threadIdx.x; j < count; j += blockDim.x) atomicAdd(&cnt[dg(keys[j])], 1u);
 }
 
+// A chunk's keys (and payloads) from ONE piece of memory, RAW: a ragged chunk reads a clamped index and chunk_pad() makes the padding
+// keys afterwards -- so a kernel can put the loads in flight before it knows the digit (the pool form's passes, vrs_msd_pool.hip).
+// stream_in (workgroup-uniform): the pass's input is larger than the caches and nobody reads it again -- nontemporal loads, which
+// leave the memory-side cache to what the pass WRITES (the next kernel reads that): 10^8 keys, contract scatter 138 -> 128 us, the
+// MSD passes 146 -> 140, the pool form's first pass 154 -> 143; below about 3e7 keys everything fits the caches and it costs a
+// little instead (10^7 keys: 0.108 -> 0.111 ms), so the callers switch it by size
+template <typename K, int ITEMS, bool PAIRS, bool FULL>
+__device__ __forceinline__ void chunk_load(const K *kin, const uint32_t *vin, uint32_t valid, bool stream_in, K (&key)[ITEMS], uint32_t (&val)[PAIRS ? ITEMS : 1]) {
+    const uint32_t seg = (threadIdx.x >> 6) * (ITEMS * 64) + (threadIdx.x & 63u);
+    if (FULL && stream_in) {
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) key[i] = __builtin_nontemporal_load(kin + seg + i * 64);
+        if constexpr (PAIRS) {
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) val[i] = __builtin_nontemporal_load(vin + seg + i * 64);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            const uint32_t idx = seg + i * 64;
+            key[i] = kin[FULL ? idx : (idx < valid ? idx : valid - 1u)];  // (unpredicated load from a clamped index)
+        }
+        if constexpr (PAIRS) {
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                const uint32_t idx = seg + i * 64;
+                val[i] = vin[FULL ? idx : (idx < valid ? idx : valid - 1u)];
+            }
+        }
+    }
+}
+// positions behind `valid`: the padding key (all ones, seen from the digit's base) has the largest digit under every shift and the
+// highest chunk indices, so it ranks behind every real key
+template <typename K, int ITEMS, typename DG>
+__device__ __forceinline__ void chunk_pad(K (&key)[ITEMS], uint32_t valid, const DG &dg) {
+    const uint32_t seg = (threadIdx.x >> 6) * (ITEMS * 64) + (threadIdx.x & 63u);
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) key[i] = seg + i * 64 < valid ? key[i] : dg.template pad<K>();
+}
+
 // `run_off`: thread t (< 256) holds the running global offset of digit t, advanced by this chunk's
 // count of t.  `valid`: number of real keys in the chunk (the rest is padding that sorts last).
 // FULL: valid == ITEMS*WAVES*64 is known, so no load or store is predicated.
@@ -412,75 +454,15 @@ __device__ __forceinline__ void recount_keys(uint32_t *cnt, const K *keys, uint3
 // LB: StreamLookback obtains the digit offsets by decoupled look-back instead of from `run_off`.
 // SRC (PieceSrc): the chunk's keys lie in several PIECES of two buffers -- the second MSD pass of the pool form reads a top byte's
 // keys from the eight slices' primary and overflow regions, and a tile may straddle their ends.
-template <typename K, int ITEMS, int WAVES, bool PAIRS, int RANK, bool FULL, typename DG, typename LB = NoLookback, typename SRC = NoPieces>
-__device__ __forceinline__ void scatter_chunk(ChunkSmem<K, ITEMS, WAVES, PAIRS> &sm, const K *kin,
-                                              const uint32_t *vin, K *kout, uint32_t *vout,
-                                              uint32_t valid, const DG &dg, uint32_t &run_off, const LB lb = {},
-                                              const SRC src = {}, bool stream_in = false) {
+// scatter_chunk_loaded: the same with the chunk's keys (payloads) in registers already -- chunk_load() and, for a ragged chunk, chunk_pad().
+template <typename K, int ITEMS, int WAVES, bool PAIRS, int RANK, bool FULL, typename DG, typename LB = NoLookback>
+__device__ __forceinline__ void scatter_chunk_loaded(ChunkSmem<K, ITEMS, WAVES, PAIRS> &sm, K (&key)[ITEMS], uint32_t (&val)[PAIRS ? ITEMS : 1], K *kout,
+                                                     uint32_t *vout, uint32_t valid, const DG &dg, uint32_t &run_off, const LB lb = {}) {
     constexpr uint32_t THREADS = WAVES * 64;
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
     const uint32_t wave = tid >> 6;
 
-    VRS_MARK(0);
-    K key[ITEMS];
-    uint32_t val[PAIRS ? ITEMS : 1];
-    const uint32_t seg = wave * (ITEMS * 64) + lane;
-    // stream_in (workgroup-uniform): the pass's input is larger than the caches and nobody reads it again -- nontemporal loads, which
-    // leave the memory-side cache to what the pass WRITES (the next kernel reads that): 10^8 keys, contract scatter 138 -> 128 us, the
-    // MSD passes 146 -> 140, the pool form's first pass 154 -> 143; below about 3e7 keys everything fits the caches and it costs a
-    // little instead (10^7 keys: 0.108 -> 0.111 ms), so the callers switch it by size
-    if (FULL && !SRC::kEnabled && stream_in) {
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) key[i] = __builtin_nontemporal_load(kin + seg + i * 64);
-        if constexpr (PAIRS) {
-#pragma unroll
-            for (int i = 0; i < ITEMS; ++i) val[i] = __builtin_nontemporal_load(vin + seg + i * 64);
-        }
-    } else if constexpr (SRC::kEnabled) {
-        // every position's virtual slot first (a scalar loop over the pieces the chunk touches: usually two or three), then all loads at once
-        uint32_t vs[ITEMS];
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) vs[i] = src.first_slot;  // (positions behind `valid`: some readable slot)
-#pragma unroll 1
-        for (uint32_t p = src.p0; p < src.p1; ++p) {
-            const uint32_t lo = __builtin_amdgcn_readlane(src.lo, p), len = __builtin_amdgcn_readlane(src.len, p), vd = __builtin_amdgcn_readlane(src.slot, p);
-#pragma unroll
-            for (int i = 0; i < ITEMS; ++i) {
-                const uint32_t idx = seg + i * 64;
-                vs[i] = idx - lo < len ? vd + (idx - lo) : vs[i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            const K k = *src.at(vs[i]);
-            key[i] = (FULL || seg + i * 64 < valid) ? k : dg.template pad<K>();
-        }
-        if constexpr (PAIRS) {
-#pragma unroll
-            for (int i = 0; i < ITEMS; ++i) val[i] = *src.val_at(vs[i]);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            const uint32_t idx = seg + i * 64;
-            if constexpr (FULL) {
-                key[i] = kin[idx];
-            } else {
-                // unpredicated load from a clamped index, then select: the padding key (all ones, seen from the digit's base) has
-                // the largest digit under every shift and the highest chunk indices, so it ranks behind every real key
-                const K k = kin[idx < valid ? idx : valid - 1u];
-                key[i] = idx < valid ? k : dg.template pad<K>();
-            }
-        }
-        if constexpr (PAIRS) {
-#pragma unroll
-            for (int i = 0; i < ITEMS; ++i) {
-                const uint32_t idx = seg + i * 64;
-                val[i] = vin[FULL ? idx : (idx < valid ? idx : valid - 1u)];
-            }
-        }
-    }
     {
         uint32_t *z = &sm.whist[0][0];
 #pragma unroll
@@ -659,6 +641,45 @@ __device__ __forceinline__ void scatter_chunk(ChunkSmem<K, ITEMS, WAVES, PAIRS> 
         }
     }
     // the next chunk's first barrier (after it zeroes the counters) separates these LDS reads from its writes
+}
+
+template <typename K, int ITEMS, int WAVES, bool PAIRS, int RANK, bool FULL, typename DG, typename LB = NoLookback, typename SRC = NoPieces>
+__device__ __forceinline__ void scatter_chunk(ChunkSmem<K, ITEMS, WAVES, PAIRS> &sm, const K *kin,
+                                              const uint32_t *vin, K *kout, uint32_t *vout,
+                                              uint32_t valid, const DG &dg, uint32_t &run_off, const LB lb = {},
+                                              const SRC src = {}, bool stream_in = false) {
+    VRS_MARK(0);
+    K key[ITEMS];
+    uint32_t val[PAIRS ? ITEMS : 1];
+    if constexpr (SRC::kEnabled) {
+        const uint32_t seg = (threadIdx.x >> 6) * (ITEMS * 64) + (threadIdx.x & 63u);
+        // every position's virtual slot first (a scalar loop over the pieces the chunk touches: usually two or three), then all loads at once
+        uint32_t vs[ITEMS];
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) vs[i] = src.first_slot;  // (positions behind `valid`: some readable slot)
+#pragma unroll 1
+        for (uint32_t p = src.p0; p < src.p1; ++p) {
+            const uint32_t lo = __builtin_amdgcn_readlane(src.lo, p), len = __builtin_amdgcn_readlane(src.len, p), vd = __builtin_amdgcn_readlane(src.slot, p);
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                const uint32_t idx = seg + i * 64;
+                vs[i] = idx - lo < len ? vd + (idx - lo) : vs[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            const K k = *src.at(vs[i]);
+            key[i] = (FULL || seg + i * 64 < valid) ? k : dg.template pad<K>();
+        }
+        if constexpr (PAIRS) {
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) val[i] = *src.val_at(vs[i]);
+        }
+    } else {
+        chunk_load<K, ITEMS, PAIRS, FULL>(kin, vin, valid, stream_in, key, val);
+        if constexpr (!FULL) chunk_pad(key, valid, dg);
+    }
+    scatter_chunk_loaded<K, ITEMS, WAVES, PAIRS, RANK, FULL, DG, LB>(sm, key, val, kout, vout, valid, dg, run_off, lb);
 }
 
 // the hybrid forms (K5b in vrs_msd_hybrid.hip, vrs_msd_pool.hip): an MSD partition by the top kMsdBits bits of the key range

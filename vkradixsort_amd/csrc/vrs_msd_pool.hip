@@ -211,7 +211,11 @@ struct PoolReserve {
         reserved_yet = true;
         cnt = v - pad_keys;
         if (cnt) reserved = __hip_atomic_fetch_add(cursor, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        rb = region[0];  // four L2-resident words, in flight beside the atomic while the keys are re-bucketed
+    }
+    // the region's four words do not depend on the keys: the kernel asks for them behind its key loads, and only the atomic add
+    // stays behind the scan
+    __device__ __forceinline__ void load_region() {
+        rb = region[0];
         rc = region[8 * 256];
         ob = region[16 * 256];
         oc = region[24 * 256];
@@ -230,12 +234,13 @@ struct PoolReserve {
         } else if (reserved >= rc) {
             bad = end - rc > oc;
             g = n_virt + ob + (reserved - rc) - excl;
+            if (cnt) atomicOr(flags, 2u);  // a run in overflow slots: the tile takes the slow store()
         } else {  // the one run of this region that crosses the end of its primary part
             bad = end - rc > oc;
             sp = excl + (rc - reserved);
             g = rb + reserved - excl;
             g2 = n_virt + ob - sp;
-            atomicOr(flags, 1u);
+            atomicOr(flags, 3u);
         }
         // a region out of room: the sort is refused (the keys of this run still go somewhere inside the scratch: store())
         if (cnt && bad) __hip_atomic_fetch_or(fail_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -246,7 +251,14 @@ struct PoolReserve {
     template <typename K, int ITEMS, uint32_t THREADS, bool FULL, typename DG>
     __device__ __forceinline__ void store(const uint32_t *, const K (&key)[ITEMS], uint32_t (&dst)[ITEMS], K *kout, uint32_t valid, const DG &dg) const {
         const uint32_t tid = threadIdx.x;
-        if (*flags & 1u) {  // workgroup-uniform
+        const uint32_t f = *flags;  // workgroup-uniform
+        if (f == 0u) {  // every run of the tile lies in primary slots (nearly every tile of a sort the sample judged well): the plain write-out
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i)
+                if (FULL || i * THREADS + tid < valid) kout[dst[i]] = key[i];
+            return;
+        }
+        if (f & 1u) {
 #pragma unroll
             for (int i = 0; i < ITEMS; ++i) {
                 const uint32_t d = dg(key[i]);
@@ -264,6 +276,12 @@ struct PoolReserve {
     template <int ITEMS, uint32_t THREADS, bool FULL>
     __device__ __forceinline__ void store_values(const uint32_t (&val)[ITEMS], const uint32_t (&dst)[ITEMS], uint32_t *vout, uint32_t valid) const {
         const uint32_t tid = threadIdx.x;
+        if (*flags == 0u) {  // (as store())
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i)
+                if (FULL || i * THREADS + tid < valid) vout[dst[i]] = val[i];
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < ITEMS; ++i) {
             uint32_t *p = dst[i] < n_virt ? vout + dst[i] : overflow_values + min(dst[i] - n_virt, overflow_last);
@@ -285,10 +303,6 @@ struct PoolLookback : StreamLookback {
             at.reserved_yet = true;
             at.cnt = v - at.pad_keys;
             if (at.cnt) __hip_atomic_fetch_add(at.cursor, at.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            at.rb = at.region[0];
-            at.rc = at.region[8 * 256];
-            at.ob = at.region[16 * 256];
-            at.oc = at.region[24 * 256];
         }
         StreamLookback::publish(v);
     }
@@ -314,6 +328,75 @@ __device__ __forceinline__ uint32_t xcc_place(unsigned long long xcc_map) {
     return x;
 }
 
+// A word of the plan that a kernel BEFORE this one wrote and that nobody writes while this one runs, at a workgroup-uniform address:
+// read through the scalar cache (a load of the constant address space), so that it waits for no vector load and none waits for it.
+__device__ __forceinline__ uint32_t plan_word(const uint32_t *p) {
+    return *(const uint32_t __attribute__((address_space(4))) *)(p);
+}
+__device__ __forceinline__ uint2 plan_word(const uint2 *p) {
+    typedef uint32_t pair_t __attribute__((ext_vector_type(2)));
+    const pair_t v = *(const pair_t __attribute__((address_space(4))) *)(p);
+    return make_uint2(v.x, v.y);
+}
+
+// One tile of the first pass.  Nothing stands in front of the key loads: their addresses need kernel arguments and the XCC alone.
+// The plan's words (armed, shift), the placement check and the claim come behind them -- an unarmed or misplaced workgroup has then
+// loaded (in bounds) keys it never uses.
+template <bool PAIRS, bool FULL>
+__device__ __forceinline__ void pool_pass_a_tile(ChunkSmem<uint32_t, 16, 8, PAIRS> &sm, uint32_t *gbase2, uint32_t *split, uint32_t *flags, const uint32_t *kin,
+                                                 const uint32_t *vin, const uint32_t *slice_keys, uint32_t *keys_out, uint32_t *overflow, uint32_t n,
+                                                 uint32_t key_base, PoolPlan *pool, MsdPlan *msd, uint32_t s_out, uint32_t i, uint32_t done, uint32_t valid,
+                                                 uint32_t armed, uint32_t shift, uint32_t overflow_capacity, uint32_t par, const PoolPayloads &pv, uint32_t top_bits) {
+    const bool stream_in = static_cast<size_t>(n) * sizeof(uint32_t) >= kStreamInBytes;  // (inputs beyond the caches: vrs_device.hpp)
+    VRS_MARK(0);
+    uint32_t key[16], val[PAIRS ? 16 : 1];
+    chunk_load<uint32_t, 16, PAIRS, FULL>(kin, vin, valid, stream_in, key, val);
+    const uint32_t d = threadIdx.x & 255u, row = s_out & 7u;
+    PoolReserve at;
+    at.region = &pool->base[row][d];
+    at.load_region();
+    // (the loads above stay above: left alone, the compiler sinks them below the returns that follow, where their values are first used)
+    asm volatile("" : : "s"(kin), "s"(vin), "s"(pool) : "memory");
+    if (armed == 0u) return;  // uniform: the sample kernel did not lay regions out (key range below 27 bits)
+    if (s_out == 8u) {  // behind an L2 the probe never saw: no row is safe to add to -- the sort is refused
+        if (threadIdx.x == 0) __hip_atomic_fetch_or(&pool->fail[par], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(&pool->claim_a[s_out * kPoolMaxTilesA + i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // (L2-local: every claim on this word comes from this XCC)
+    if (threadIdx.x == 0) *flags = 0;  // (set behind the chunk's barriers, read behind its last one)
+    RadixDigit<uint32_t> dg;
+    dg.shift = shift + (kMsdBits - top_bits);
+    dg.base = key_base;
+    if constexpr (!FULL) chunk_pad(key, valid, dg);
+    at.cursor = &msd->cursor_a[s_out][d];
+    at.pad_keys = d == dg(dg.template pad<uint32_t>()) ? kPoolTile - valid : 0u;  // (the padding key carries the largest digit: 255, or 127 of 7 bits)
+    at.n_virt = n;
+    at.overflow = overflow;
+    at.overflow_last = overflow_capacity - 1u;
+    at.gbase2 = gbase2;
+    at.split = split;
+    at.flags = flags;
+    at.fail_word = &pool->fail[par];
+    uint32_t unused = 0;
+    if constexpr (PAIRS) {
+        // payloads: the tile's place in (slice, top byte)'s share is its rank there (PoolLookback) -- one chain per slice, row i of it
+        at.overflow_values = pv.overflow_values;
+        PoolLookback lb;
+        lb.at = at;
+        lb.stream_keys = slice_keys;
+        lb.done = done;
+        lb.col = pv.status + static_cast<size_t>(s_out) * kBins + d;
+        lb.stride = static_cast<size_t>(8) * kBins;
+        lb.index = static_cast<int>(i);
+        lb.tag = 1u << kLbTagShift;
+        lb.budget = pv.spin_budget;
+        lb.hold = pv.hold_tile >= 0 && i == static_cast<uint32_t>(pv.hold_tile);
+        scatter_chunk_loaded<uint32_t, 16, 8, true, RANK_ATOMIC, FULL>(sm, key, val, keys_out, pv.values_partner, valid, dg, unused, lb);
+    } else {
+        scatter_chunk_loaded<uint32_t, 16, 8, false, RANK_ATOMIC, FULL>(sm, key, val, keys_out, nullptr, valid, dg, unused, at);
+    }
+}
+
 // grid = 8 * tiles_per_stream workgroups; a workgroup on the XCC of place x takes tile b >> 3 of slice x -- the slice whose keys the
 // sample counted for the regions of row x, the row whose cursors live in this CU's L2.  (Observed placement: block b on the XCC of
 // place (b + r) % 8 with r fixed for a queue -- and a stream may move to another queue: r at the probe is not r now.  Nothing but
@@ -326,63 +409,30 @@ __global__ __launch_bounds__(512, 4) void pool_pass_a_kernel(const uint32_t *__r
                                                              PoolPayloads pv, uint32_t top_bits) {
     __shared__ ChunkSmem<uint32_t, 16, 8, PAIRS> sm;
     __shared__ uint32_t s_gbase2[kBins], s_split[kBins], s_flags;
-    if (pool->armed == 0u) return;  // uniform: the sample kernel did not lay regions out (key range below 27 bits)
+    VRS_MARK(6);
+    const uint32_t armed = plan_word(&pool->armed), shift = plan_word(&pool->shift);  // (asked for now, looked at behind the key loads)
     const uint32_t i = blockIdx.x >> 3;
     const uint32_t s_out = xcc_place(xcc_map);
-    if (s_out == 8u) {  // behind an L2 the probe never saw: no row is safe to add to -- the sort is refused
-        if (threadIdx.x == 0) __hip_atomic_fetch_or(&pool->fail[par], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(&pool->claim_a[s_out * kPoolMaxTilesA + i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // (L2-local: every claim on this word comes from this XCC)
     // misplace (test hook): odd tiles are read from the neighbouring slice
-    const uint32_t s_in = (s_out + (misplace ? (i & 1u) : 0u)) & 7u;
+    const uint32_t s_in = (s_out + (misplace ? (i & 1u) : 0u)) & 7u;  // (an XCC the probe never saw: some slice, for the loads' sake)
     const uint32_t len = ps.len[s_in];
     const uint32_t done = i * kPoolTile;
-    if (done >= len) return;
-    if (threadIdx.x == 0) s_flags = 0;  // (set behind the chunk's barriers, read behind its last one)
-    const uint32_t valid = min(kPoolTile, len - done);
-    const uint32_t *kin = keys_in + ps.start[s_in] + done;
-    const uint32_t d = threadIdx.x & 255u;
-    RadixDigit<uint32_t> dg;
-    dg.shift = pool->shift + (kMsdBits - top_bits);
-    dg.base = key_base;
-    PoolReserve at;
-    at.cursor = &msd->cursor_a[s_out][d];
-    at.region = &pool->base[s_out][d];
-    at.pad_keys = d == dg(dg.template pad<uint32_t>()) ? kPoolTile - valid : 0u;  // (the padding key carries the largest digit: 255, or 127 of 7 bits)
-    at.n_virt = n;
-    at.overflow = overflow;
-    at.overflow_last = overflow_capacity - 1u;
-    at.gbase2 = s_gbase2;
-    at.split = s_split;
-    at.flags = &s_flags;
-    at.fail_word = &pool->fail[par];
-    uint32_t unused = 0;
-    const bool stream_in = static_cast<size_t>(n) * sizeof(uint32_t) >= kStreamInBytes;  // (inputs beyond the caches: vrs_device.hpp)
-    if constexpr (PAIRS) {
-        // payloads: the tile's place in (slice, top byte)'s share is its rank there (PoolLookback) -- one chain per slice, row i of it
-        at.overflow_values = pv.overflow_values;
-        PoolLookback lb;
-        lb.at = at;
-        lb.stream_keys = keys_in + ps.start[s_in];
-        lb.done = done;
-        lb.col = pv.status + static_cast<size_t>(s_out) * kBins + d;
-        lb.stride = static_cast<size_t>(8) * kBins;
-        lb.index = static_cast<int>(i);
-        lb.tag = 1u << kLbTagShift;
-        lb.budget = pv.spin_budget;
-        lb.hold = pv.hold_tile >= 0 && i == static_cast<uint32_t>(pv.hold_tile);
-        const uint32_t *vin = pv.values_home + ps.start[s_in] + done;
-        if (valid == kPoolTile)
-            scatter_chunk<uint32_t, 16, 8, true, RANK_ATOMIC, true>(sm, kin, vin, keys_out, pv.values_partner, valid, dg, unused, lb, NoPieces{}, stream_in);
-        else
-            scatter_chunk<uint32_t, 16, 8, true, RANK_ATOMIC, false>(sm, kin, vin, keys_out, pv.values_partner, valid, dg, unused, lb);
-    } else {
-        if (valid == kPoolTile)
-            scatter_chunk<uint32_t, 16, 8, false, RANK_ATOMIC, true>(sm, kin, nullptr, keys_out, nullptr, valid, dg, unused, at, NoPieces{}, stream_in);
-        else
-            scatter_chunk<uint32_t, 16, 8, false, RANK_ATOMIC, false>(sm, kin, nullptr, keys_out, nullptr, valid, dg, unused, at);
+    const uint32_t valid = done < len ? min(kPoolTile, len - done) : 0u;
+    const uint32_t *slice_keys = keys_in + ps.start[s_in];
+    const uint32_t *vin = PAIRS ? pv.values_home + ps.start[s_in] + done : nullptr;
+    if (valid == kPoolTile)
+        pool_pass_a_tile<PAIRS, true>(sm, s_gbase2, s_split, &s_flags, slice_keys + done, vin, slice_keys, keys_out, overflow, n, key_base, pool, msd, s_out, i,
+                                      done, valid, armed, shift, overflow_capacity, par, pv, top_bits);
+    else if (valid != 0u)
+        pool_pass_a_tile<PAIRS, false>(sm, s_gbase2, s_split, &s_flags, slice_keys + done, vin, slice_keys, keys_out, overflow, n, key_base, pool, msd, s_out, i,
+                                       done, valid, armed, shift, overflow_capacity, par, pv, top_bits);
+    else if (armed != 0u) {  // a tile behind its slice's end: nothing to load, but its claim is owed like any other's
+        if (s_out == 8u) {
+            if (threadIdx.x == 0) __hip_atomic_fetch_or(&pool->fail[par], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if (threadIdx.x == 0)
+            __hip_atomic_fetch_add(&pool->claim_a[s_out * kPoolMaxTilesA + i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
+    VRS_MARK_FLUSH(1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -661,7 +711,7 @@ struct SlackReserve {
     uint32_t done = 0;
     uint32_t seed = 0;
     uint32_t *cursor = nullptr;      // this thread's bucket's cursor
-    uint32_t start = 0, cap = 0;     // the bucket's region: first slot, its slots
+    uint32_t start = 0, next = 0;    // the bucket's region: its first slot, the next region's (its slots: the difference, taken when both have arrived)
     uint32_t local_cap = 0;          // keys the enqueued local sort takes per bucket
     uint32_t *max_bucket = nullptr;
     uint32_t dump = 0;               // first slot of the dump tile
@@ -684,7 +734,7 @@ struct SlackReserve {
     __device__ __forceinline__ void place(uint32_t *gbase, uint32_t tid, uint32_t, uint32_t excl) const { place_run(gbase, tid, reserved, excl); }
     __device__ __forceinline__ void place_run(uint32_t *gbase, uint32_t tid, uint32_t reserved, uint32_t excl) const {
         const uint32_t end = reserved + cnt;
-        const bool bad = cnt != 0u && end > cap;
+        const bool bad = cnt != 0u && end > next - start;
         if (bad) {
             __hip_atomic_fetch_or(fail_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else if (cnt != 0u && end > local_cap) {
@@ -751,10 +801,22 @@ __global__ __launch_bounds__(512, PAIRS ? 4 : 6) void pool_pass_b_kernel(const u
                                                              unsigned long long xcc_map, uint32_t stamp, uint32_t grouped, uint32_t par, PoolPayloads pv,
                                                              uint32_t top_bits) {
     __shared__ ChunkSmem<uint32_t, 16, 8, PAIRS> sm;
+    VRS_MARK(6);
     // the list follows the XCC this workgroup RUNS on (pool_pass_a_kernel): all tiles of a top byte then meet behind the L2 that
     // holds its 64 cursors, whatever the dispatcher's rotation
-    const uint32_t x = xcc_place(xcc_map), j = blockIdx.x >> 3;
-    if (pool->ok_a == 0u) return;  // uniform (enqueued before the plan was known: it may have said no)
+    const uint32_t x = xcc_place(xcc_map), xs = x & 7u, j = blockIdx.x >> 3;
+    // Everything the key loads wait for, in ONE round trip through the scalar cache: the plan's verdict, the list's length and which
+    // tile (one word pair of the plan kernel's map; its second word: the top byte and the tile's index in it); with them the two
+    // words the tile's set-up needs.  (A list entry of a plan that said no may be anything: no load before the verdict is known.)
+    const uint32_t ok_a = plan_word(&pool->ok_a), tiles = plan_word(&pool->tiles_b[xs][32]);
+    const uint2 entry = plan_word(&pool->tile_map[xs][j < kPoolMaxTilesB ? j : 0u]);
+    const uint32_t total = plan_word(&pool->top_base[256]), shift = plan_word(&pool->shift);
+    // (one wait for all of them, and for the kernel's arguments, here: left alone, the compiler sinks every load to its first use -- a
+    // round trip in front of each of the three returns below, and one more for the arguments)
+    asm volatile("" : : "s"(ok_a), "s"(tiles), "s"(entry.x), "s"(entry.y), "s"(total), "s"(shift), "s"(regions), "s"(overflow), "s"(slack), "s"(n_virt), "s"(stamp),
+                 "s"(top_bits), "s"(key_base), "s"(local_cap), "s"(dump), "s"(grouped), "s"(par)
+                 : "memory");
+    if (ok_a == 0u) return;  // uniform (enqueued before the plan was known: it may have said no)
     if (x == 8u) {  // behind an L2 the probe never saw
         if (threadIdx.x == 0) __hip_atomic_fetch_or(&pool->fail[par], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
@@ -762,34 +824,71 @@ __global__ __launch_bounds__(512, PAIRS ? 4 : 6) void pool_pass_b_kernel(const u
     // the claim: this sort's stamp into (list, tile)'s word -- asked for now, looked at when the tile's loads are under way
     uint32_t claimed = 0;
     if (threadIdx.x == 0) claimed = __hip_atomic_exchange(&pool->claim_b[j * 8u + x], stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // (L2-local: a second claim comes from this XCC too)
-    // which tile: one word pair of the plan kernel's map (its second word: the top byte and the tile's index in it)
-    const uint2 entry = pool->tile_map[x][j < kPoolMaxTilesB ? j : 0u];
-    if (j >= pool->tiles_b[x][32]) return;
+    if (j >= tiles) return;
     const uint32_t a = entry.y & 255u, tile_lo = (entry.y >> 8) * kPoolTile;
     const bool one_piece = entry.x != kPoolTileGeneral;  // uniform: a full tile inside one piece -- its loads wait for nothing else
+    const bool stream_in = static_cast<size_t>(total) * sizeof(uint32_t) >= kStreamInBytes;
+    constexpr uint32_t SUB = 1u << SUBBITS;
+    const uint32_t d = threadIdx.x & 255u, b = a * SUB + min(d, SUB - 1u);
+    const BitsDigit dg{shift + kMsdBits - top_bits - SUBBITS, SUB - 1u, key_base};  // (key_base is a multiple of 2^24 and the bits end at or below bit 24)
+    SlackReserve at;
+    // what every tile sets up; asked for BEHIND the key loads of a tile in one piece (nothing of it is needed before the scan)
+    auto set_up = [&](uint32_t valid) {
+        at.cursor = &pool->sub_cursor[b];
+        at.start = pool->sub_start[b];  // (every thread, no branch: a thread that reserves nothing reads the last bucket's)
+        at.next = pool->sub_start[b + 1u];
+        at.local_cap = local_cap;
+        at.max_bucket = &pool->max_bucket;
+        at.dump = dump;
+        at.pad_keys = d == SUB - 1u ? kPoolTile - valid : 0u;  // (the padding key, key_base - 1, carries the largest digit)
+        // a sort: no key may have bits above the probed range; grouped keys (the caller's promise): every key of this tile carries top byte a
+        at.above = grouped ? 0xFF000000u : (shift + kMsdBits < 32u ? ~0u << (shift + kMsdBits) : 0u);
+        at.key_base = grouped ? key_base + (a << 24) : key_base;
+        at.fail_word = &pool->fail[par];
+        // (two workgroups of one group of eight on ONE XCC: the tile has been taken twice and another not at all)
+        if (threadIdx.x == 0 && claimed == stamp) __hip_atomic_fetch_or(&pool->fail[par], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto chain = [&](SlackLookback &lb) {
+        // payloads: the tile's place in a bucket is its rank there (SlackLookback) -- the chain of top byte a: the rows of its tiles
+        // in list x, 8 rows apart (tile i of the top byte is tile j of the list)
+        lb.at = at;
+        lb.col = pv.status + (static_cast<size_t>(j - (entry.y >> 8)) * 8u + x) * kBins + d;
+        lb.stride = static_cast<size_t>(8) * kBins;
+        lb.index = static_cast<int>(entry.y >> 8);
+        lb.tag = 6u << kLbTagShift;
+        lb.budget = pv.spin_budget;
+    };
+    uint32_t unused = 0;
+    if (one_piece) {  // five tiles in six
+        const uint32_t slot0 = entry.x;
+        const uint32_t *kin = slot0 < n_virt ? regions + slot0 : overflow + (slot0 - n_virt);
+        const uint32_t *vin = !PAIRS ? nullptr : slot0 < n_virt ? pv.values_partner + slot0 : pv.overflow_values + (slot0 - n_virt);
+        VRS_MARK(0);
+        uint32_t key[16], val[PAIRS ? 16 : 1];
+        chunk_load<uint32_t, 16, PAIRS, true>(kin, vin, kPoolTile, stream_in, key, val);
+        asm volatile("" : "+v"(claimed) : : "memory");  // (the claim's answer is looked at BEHIND the loads: the compiler had the compare, and a wait for it, in front)
+        set_up(kPoolTile);
+        if constexpr (PAIRS) {
+            SlackLookback lb;
+            chain(lb);
+            scatter_chunk_loaded<uint32_t, 16, 8, true, RANK_ATOMIC, true, BitsDigit, SlackLookback>(sm, key, val, slack, pv.slack_values, kPoolTile, dg, unused, lb);
+        } else {
+            scatter_chunk_loaded<uint32_t, 16, 8, false, RANK_ATOMIC, true, BitsDigit, SlackReserve>(sm, key, val, slack, nullptr, kPoolTile, dg, unused, at);
+        }
+        VRS_MARK_FLUSH(2);
+        return;
+    }
     // The top byte's keys lie in 16 PIECES: slice s's primary region (piece 2 s), then its overflow region (2 s + 1).  A tile that
     // touches several: every wave, lane p = piece p -- its keys, its first (virtual) slot, where it starts in the top byte's run of keys
     // (the plan kernel's row of the top byte: 128 bytes, one load per wave).
     const uint32_t lane = threadIdx.x & 63u;
-    uint2 pc = make_uint2(0, 0);
-    if (!one_piece) pc = pool->pieces[a][lane & 15u];
-    const uint32_t shift = pool->shift;
-    constexpr uint32_t SUB = 1u << SUBBITS;
-    const uint32_t d = threadIdx.x & 255u, b = a * SUB + min(d, SUB - 1u);
-    SlackReserve at;
-    at.cursor = &pool->sub_cursor[b];
-    if (threadIdx.x < SUB) {  // (the threads that reserve: one per bucket of the top byte)
-        at.start = pool->sub_start[b];
-        at.cap = pool->sub_start[b + 1u] - at.start;
-    }
-    at.local_cap = local_cap;
-    at.max_bucket = &pool->max_bucket;
+    const uint2 pc = pool->pieces[a][lane & 15u];
     const uint32_t pend = pc.x, pslot = pc.y;
     const uint32_t before = __shfl_up(pend, 1);
     const uint32_t plo = lane == 0u ? 0u : before;  // the piece holds positions [plo, pend) of the top byte
     const uint32_t plen = lane < 16u ? pend - plo : 0u;
     const uint32_t keys_a = __builtin_amdgcn_readlane(pend, 15);
-    const uint32_t valid = one_piece ? kPoolTile : min(kPoolTile, keys_a - tile_lo);
+    const uint32_t valid = min(kPoolTile, keys_a - tile_lo);
     const unsigned long long touch = __ballot(plen != 0u && plo < tile_lo + valid && pend > tile_lo);
     PieceSrc src;
     src.p0 = static_cast<uint32_t>(__builtin_ctzll(touch | (1ull << 63)));
@@ -800,47 +899,24 @@ __global__ __launch_bounds__(512, PAIRS ? 4 : 6) void pool_pass_b_kernel(const u
     src.regions = regions;
     src.overflow = overflow;
     src.n_virt = n_virt;
-    const uint32_t slot0 = one_piece ? entry.x : __builtin_amdgcn_readlane(pslot, src.p0) + (tile_lo - __builtin_amdgcn_readlane(plo, src.p0));  // the tile's first key
-    src.first_slot = slot0;
-    const BitsDigit dg{shift + kMsdBits - top_bits - SUBBITS, SUB - 1u, key_base};  // (key_base is a multiple of 2^24 and the bits end at or below bit 24)
-    at.dump = dump;
-    at.pad_keys = d == SUB - 1u ? kPoolTile - valid : 0u;  // (the padding key, key_base - 1, carries the largest digit)
-    // a sort: no key may have bits above the probed range; grouped keys (the caller's promise): every key of this tile carries top byte a
-    at.above = grouped ? 0xFF000000u : (shift + kMsdBits < 32u ? ~0u << (shift + kMsdBits) : 0u);
-    at.key_base = grouped ? key_base + (a << 24) : key_base;
-    at.fail_word = &pool->fail[par];
-    uint32_t unused = 0;
-    // (two workgroups of one group of eight on ONE XCC: the tile has been taken twice and another not at all)
-    if (threadIdx.x == 0 && claimed == stamp) __hip_atomic_fetch_or(&pool->fail[par], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool stream_in = static_cast<size_t>(pool->top_base[256]) * sizeof(uint32_t) >= kStreamInBytes;
-    const uint32_t *kin = slot0 < n_virt ? regions + slot0 : overflow + (slot0 - n_virt);
+    src.first_slot = __builtin_amdgcn_readlane(pslot, src.p0) + (tile_lo - __builtin_amdgcn_readlane(plo, src.p0));  // the tile's first key
+    set_up(valid);
     if constexpr (PAIRS) {
-        // payloads: the tile's place in a bucket is its rank there (SlackLookback) -- the chain of top byte a: the rows of its tiles
-        // in list x, 8 rows apart (tile i of the top byte is tile j of the list)
         src.vregions = pv.values_partner;
         src.voverflow = pv.overflow_values;
         SlackLookback lb;
-        lb.at = at;
-        lb.col = pv.status + (static_cast<size_t>(j - (entry.y >> 8)) * 8u + x) * kBins + d;
-        lb.stride = static_cast<size_t>(8) * kBins;
-        lb.index = static_cast<int>(entry.y >> 8);
-        lb.tag = 6u << kLbTagShift;
-        lb.budget = pv.spin_budget;
-        const uint32_t *vin = slot0 < n_virt ? pv.values_partner + slot0 : pv.overflow_values + (slot0 - n_virt);
-        if (one_piece)
-            scatter_chunk<uint32_t, 16, 8, true, RANK_ATOMIC, true, BitsDigit, SlackLookback>(sm, kin, vin, slack, pv.slack_values, valid, dg, unused, lb, NoPieces{}, stream_in);
-        else if (valid == kPoolTile)
+        chain(lb);
+        if (valid == kPoolTile)
             scatter_chunk<uint32_t, 16, 8, true, RANK_ATOMIC, true, BitsDigit, SlackLookback, PieceSrc>(sm, nullptr, nullptr, slack, pv.slack_values, valid, dg, unused, lb, src);
         else
             scatter_chunk<uint32_t, 16, 8, true, RANK_ATOMIC, false, BitsDigit, SlackLookback, PieceSrc>(sm, nullptr, nullptr, slack, pv.slack_values, valid, dg, unused, lb, src);
     } else {
-        if (one_piece)  // five tiles in six
-            scatter_chunk<uint32_t, 16, 8, false, RANK_ATOMIC, true, BitsDigit, SlackReserve>(sm, kin, nullptr, slack, nullptr, valid, dg, unused, at, NoPieces{}, stream_in);
-        else if (valid == kPoolTile)
+        if (valid == kPoolTile)
             scatter_chunk<uint32_t, 16, 8, false, RANK_ATOMIC, true, BitsDigit, SlackReserve, PieceSrc>(sm, nullptr, nullptr, slack, nullptr, valid, dg, unused, at, src);
         else  // the top byte's ragged last tile
             scatter_chunk<uint32_t, 16, 8, false, RANK_ATOMIC, false, BitsDigit, SlackReserve, PieceSrc>(sm, nullptr, nullptr, slack, nullptr, valid, dg, unused, at, src);
     }
+    VRS_MARK_FLUSH(2);
 }
 
 }  // namespace

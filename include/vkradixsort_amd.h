@@ -579,6 +579,66 @@ int vrs_bin_count_stats(vrs_context ctx, uint64_t *lds_calls, uint64_t *global_c
 int vrs_bin_linear_host(const void *values, uint64_t num_values, int dtype, double lo, double hi, uint32_t num_bins, int64_t *bins);
 
 /*
+ * K13 -- segmented reduction over rows (build extension; no reference counterpart): torch.segment_reduce, and the sum behind
+ * index_add / index_reduce / scatter_reduce once the contributions are sorted by destination.  `values`: num_rows rows of row_width
+ * elements of `dtype` (int32, int64, float16, bfloat16, float32 or float64 of vrs_sort_dtype); element (row, column) sits at
+ * (size_t)row * row_width + column.  `order`: NULL, or num_rows uint32 -- reduction row i is then values row order[i] (an entry beyond
+ * num_rows - 1 reads row num_rows - 1).  `offsets`: num_segments + 1 uint32 that index reduction rows; segment s is the reduction rows
+ * [offsets[s], offsets[s+1]) clamped exactly as vrs_segment_tier_for clamps it.  out row s = op over the segment's rows, column by
+ * column; with `init` (num_segments rows) op(init row s, that); a segment without rows answers init's own bits, or without init the
+ * op's identity: sum 0, prod 1, min +inf (the integer type's maximum), max -inf (the type's minimum).  min and max answer NaN when any
+ * row holds one, as torch; integer sums and products wrap.
+ * THE ORDER is fixed, so the same input gives the same bits on every run, device and grid; vrs_segment_reduce_host evaluates the same
+ * functions on the host.  With CH = VRS_TUNE_REDUCE_CHUNK_ROWS and L rows: reduce(rows) = chunk(rows) when L <= CH, else reduce of the
+ * list [chunk(rows[i * CH, min(L, (i + 1) * CH))) for i = 0 ..].  Partials are kept in the accumulator type: float32 for float16 and
+ * bfloat16 values -- rounded to the value type once, at the end, to nearest even --, the value type otherwise.  chunk() starts every
+ * accumulator at the identity and has three lane maps (vrs_reduce_map), chosen from the chunk's rows and row_width alone
+ * (vrs_segment_reduce_map_for):
+ *   VRS_REDUCE_MAP_LANE     row_width < 64, at most VRS_TUNE_REDUCE_LANE_ROWS rows: one accumulator, the rows added in order
+ *   VRS_REDUCE_MAP_ROWS     row_width < 64, more rows: G = 64 / C' accumulators, C' the power of two at or above row_width; row t goes
+ *                           to accumulator t mod G, in order; then for s = G/2, G/4 .. 1: acc[g] = op(acc[g], acc[g + s]) for g < s;
+ *                           acc[0] answers.  An accumulator without a row keeps the identity, which changes nothing it meets
+ *   VRS_REDUCE_MAP_COLUMNS  row_width >= 64: one accumulator per column, the rows added in order
+ * Because every accumulator starts at +0.0, a float sum that is zero is +0.0 whatever the signs of the zeros that went in.
+ * Kernels: a classify kernel writes the work lists into `scratch` (segments of the lane map; chunk items for every level); then one
+ * launch for the lane map and one per level, whose grids are host-side bounds and whose workgroups read the real counts on the device.
+ * Level k writes the partials level k + 1 reads into `scratch`.  No float atomics anywhere.  values, order, offsets and init are never
+ * written; out may not overlap them, except that out == init is allowed; every element of out is written exactly once.
+ * scratch: at least vrs_segment_reduce_scratch_bytes(...) bytes for the context's VRS_TUNE_REDUCE_CHUNK_ROWS, contents afterwards
+ * unspecified.  The bound counts on segments that do not overlap; where clamped ranges overlap so far that it does not hold, the
+ * segments that find no room answer as segments without rows (never an access out of bounds).
+ * num_segments == 0: VRS_OK, nothing done.  A NULL context, values (when there are rows), offsets, out or scratch, an unknown dtype or
+ * op, row_width == 0, undersized buffers (values: num_rows x row_width elements; order: num_rows uint32; offsets: num_segments + 1;
+ * init, out: num_segments x row_width elements; scratch: the bound), 8-byte elements off an 8-byte boundary and an out that overlaps
+ * an input: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Stream-ordered on the context's stream; the call only enqueues
+ * (after settling a pending one-call sort) and never waits for the device.
+ */
+typedef enum vrs_reduce_op { VRS_REDUCE_SUM = 0, VRS_REDUCE_PROD = 1, VRS_REDUCE_MIN = 2, VRS_REDUCE_MAX = 3 } vrs_reduce_op;
+typedef enum vrs_reduce_map { VRS_REDUCE_MAP_LANE = 0, VRS_REDUCE_MAP_ROWS = 1, VRS_REDUCE_MAP_COLUMNS = 2 } vrs_reduce_map;
+int vrs_segment_reduce(vrs_context ctx, vrs_buffer values, uint32_t num_rows, uint32_t row_width, int dtype,
+                       vrs_buffer order /* NULL, or num_rows uint32: reduction row i is values row order[i] */,
+                       vrs_buffer offsets, uint32_t num_segments, int op,
+                       vrs_buffer init /* NULL, or num_segments x row_width values */,
+                       vrs_buffer out /* num_segments x row_width */, vrs_buffer scratch);
+/* the scratch a call needs with chunk_rows = the context's VRS_TUNE_REDUCE_CHUNK_ROWS (64 .. 4096): a pure function, needs no device.
+ * Never shrinks as num_rows grows, never grows with chunk_rows.  With a = the accumulator's bytes (8 for int64 / float64, else 4), about
+ * 4 x num_segments + 16 x (num_rows / chunk_rows + num_segments) + 2 x a x row_width x num_rows / chunk_rows bytes. */
+int vrs_segment_reduce_scratch_bytes(uint32_t num_rows, uint32_t row_width, uint32_t num_segments, int dtype, uint32_t chunk_rows,
+                                     uint64_t *bytes);
+/* the lane map of a chunk of chunk_len rows (lane_rows: VRS_TUNE_REDUCE_LANE_ROWS, 0 .. 64): a pure function, needs no device.
+ * *map = VRS_REDUCE_MAP_*. */
+int vrs_segment_reduce_map_for(uint32_t chunk_len, uint32_t row_width, uint32_t lane_rows, int *map);
+/* levels a segment of len rows takes: 1 up to chunk_rows rows (an empty segment too), one more per factor of chunk_rows.  Pure. */
+int vrs_segment_reduce_levels_for(uint32_t len, uint32_t chunk_rows, uint32_t *levels);
+/* vrs_segment_reduce on the host, by the functions the kernels compile: host pointers, the same order, the same bits.  Needs no device. */
+int vrs_segment_reduce_host(const void *values, uint64_t num_rows, uint32_t row_width, int dtype, const uint32_t *order,
+                            const uint32_t *offsets, uint32_t num_segments, int op, const void *init,
+                            uint32_t chunk_rows, uint32_t lane_rows, void *out);
+/* cumulative per context: chunks each map was given by the classification, and the most levels any segment took (waits for the
+ * context's stream; any pointer may be NULL) */
+int vrs_segment_reduce_stats(vrs_context ctx, uint64_t *lane_chunks, uint64_t *row_chunks, uint64_t *column_chunks, uint64_t *max_levels);
+
+/*
  * Run-length encoding (build extension; no reference counterpart -- the reference's callers find each cell's or tile's [start, end)
  * in the sorted ids themselves): n keys of key_bytes (4 or 8) each, in any order, as maximal runs of bit-identical consecutive keys
  * (torch.unique_consecutive).  With R runs: out_keys[j] = the key of run j, out_offsets[j] = its first position and out_offsets[R] = n,
@@ -967,6 +1027,10 @@ typedef enum vrs_tuning_key {
     VRS_TUNE_SELECT_COMPACT_DIVISOR = 34, /* one-rank selection, grid tier: after a level whose chosen bin holds at most length / value keys
                                          (and at most 1024 per 16384 keys of the segment, what its area holds) the matching keys' ranks are
                                          copied once and the later levels read the copy; 0 = never.  Default 16, not measured (DESIGN "K12") */
+    VRS_TUNE_REDUCE_CHUNK_ROWS = 35, /* segmented reduction: CH, the rows of one chunk (64 .. 4096).  Default 512, a split length known to even out
+                                        skewed lists of 1- and 2-KB rows: a first setting (DESIGN "K13") */
+    VRS_TUNE_REDUCE_LANE_ROWS = 36, /* segmented reduction, row_width < 64: chunks of up to this many rows (0 .. 64) are added by one lane per column.
+                                       Default 16, not measured (DESIGN "K13") */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

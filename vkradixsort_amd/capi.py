@@ -118,6 +118,11 @@ VRS_TUNE_BINCOUNT_LDS_BYTES = 32
 BINCOUNT_LDS_BYTES_DEFAULT, BINCOUNT_LDS_BYTES_MAX = 64 * 1024, 160 * 1024
 BINCOUNT_TILE_BYTES = 16 * 1024  # of elements, per workgroup and step of its loop
 BINCOUNT_WORKGROUPS_PER_CU = 2   # one when a workgroup's counters take more than half of BINCOUNT_LDS_BYTES_MAX
+# segmented reduction (vrs_segment_reduce): ops, lane maps (vrs_reduce_map), tuning keys and the library's defaults for them
+VRS_REDUCE_SUM, VRS_REDUCE_PROD, VRS_REDUCE_MIN, VRS_REDUCE_MAX = 0, 1, 2, 3
+VRS_REDUCE_MAP_LANE, VRS_REDUCE_MAP_ROWS, VRS_REDUCE_MAP_COLUMNS = 0, 1, 2
+VRS_TUNE_REDUCE_CHUNK_ROWS, VRS_TUNE_REDUCE_LANE_ROWS = 35, 36
+REDUCE_CHUNK_ROWS_DEFAULT, REDUCE_LANE_ROWS_DEFAULT = 512, 16
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -272,6 +277,12 @@ _SIGNATURES = [
     ("vrs_bin_count_plan", c_int, [c_void_p, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
     ("vrs_bin_count_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_bin_linear_host", c_int, [c_void_p, c_uint64, c_int, c_double, c_double, c_uint32, c_void_p]),
+    ("vrs_segment_reduce", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vrs_segment_reduce_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint64)]),
+    ("vrs_segment_reduce_map_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
+    ("vrs_segment_reduce_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
+    ("vrs_segment_reduce_host", c_int, [c_void_p, c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_uint32, c_uint32, c_void_p]),
+    ("vrs_segment_reduce_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
     ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -281,6 +281,7 @@ int vrs_context_destroy(vrs_context ctx) {
     segmented_release(ctx);
     topk_release(ctx);
     select_release(ctx);
+    reduce_release(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return VRS_OK;
@@ -715,6 +716,14 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
         case VRS_TUNE_BINCOUNT_LDS_BYTES:
             if (value < 0 || value > 160 * 1024) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the counting kernels' LDS capacity must be 0 .. 163840 bytes");
             ctx->bincount_lds_bytes = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_REDUCE_CHUNK_ROWS:
+            if (value < 64 || value > 4096) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the reduction's chunk must be 64 .. 4096 rows");
+            ctx->reduce_chunk_rows = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_REDUCE_LANE_ROWS:
+            if (value < 0 || value > 64) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the reduction's lane map takes 0 .. 64 rows");
+            ctx->reduce_lane_rows = static_cast<uint32_t>(value);
             return VRS_OK;
         case VRS_TUNE_MSD_POOL_PAIRS_PACKED:
             if (value < -1 || value > 1) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pairs' packed local sort: -1 (by size), 0 (never) or 1 (always)");

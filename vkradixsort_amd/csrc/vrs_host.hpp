@@ -26,6 +26,7 @@
 struct vrs_segmented_state;  // vrs_capi_segmented.hip
 struct vrs_topk_state;       // vrs_capi_topk.hip
 struct vrs_select_state;     // vrs_capi_select.hip
+struct vrs_reduce_state;     // vrs_capi_segreduce.hip
 
 struct vrs_context_t {
     int device = 0;
@@ -184,6 +185,10 @@ struct vrs_context_t {
     // counting (vrs_capi_bincount.hip); the default is vrs_bincount.hpp's kBinCountDefaultLdsBytes
     uint32_t bincount_lds_bytes = 64u * 1024u;    // VRS_TUNE_BINCOUNT_LDS_BYTES
     uint64_t bincount_calls[2] = {};              // calls per tier (vrs_bin_count_stats)
+    // segmented reduction (vrs_capi_segreduce.hip); the defaults are vrs_reduce_order.hpp's kReduce*Default
+    vrs_reduce_state *reduce = nullptr;
+    uint32_t reduce_chunk_rows = 512u;            // VRS_TUNE_REDUCE_CHUNK_ROWS
+    uint32_t reduce_lane_rows = 16u;              // VRS_TUNE_REDUCE_LANE_ROWS
 };
 
 struct vrs_buffer_t {
@@ -319,6 +324,7 @@ int settle_pending(vrs_context ctx);
 void segmented_release(vrs_context ctx);
 void topk_release(vrs_context ctx);
 void select_release(vrs_context ctx);
+void reduce_release(vrs_context ctx);
 
 // A context's cumulative device counters (count entries of T): made and zeroed on its stream at first use; read back once the calls
 // before have finished (all zeros when they were never made: counters == NULL).

@@ -48,6 +48,7 @@ class GPUContext:
         self.m_activeIndex = 0
         self._h = None
         self._lib = None
+        self.tuning: dict = {}
 
     def init(self) -> None:  # GPUContext.cpp:7-9
         self._lib = capi.load_library()
@@ -115,6 +116,7 @@ class GPUContext:
 
     def setTuning(self, key: int, value: int) -> None:
         self.check(self._lib.vrs_set_tuning(self.handle, key, value))
+        self.tuning[key] = value  # (what was set and accepted: the wrappers size scratch buffers from it)
 
     def __enter__(self):
         self.init()

@@ -639,6 +639,65 @@ int vrs_segment_reduce_host(const void *values, uint64_t num_rows, uint32_t row_
 int vrs_segment_reduce_stats(vrs_context ctx, uint64_t *lane_chunks, uint64_t *row_chunks, uint64_t *column_chunks, uint64_t *max_levels);
 
 /*
+ * K14 -- inclusive prefix scan over rows (build extension; no reference counterpart): torch.cumsum, cumprod, cummax and cummin.
+ * `values`: a dense [num_segments, num_rows, row_width] array of `dtype`; element (s, r, c) sits at ((size_t)s * num_rows + r) * row_width + c.
+ * Every segment is scanned down its rows, every column on its own: out[s, r, c] = values[s, 0, c] (+) .. (+) values[s, r, c].  row_width
+ * == 1 is the flat scan; a dim other than the last of a contiguous tensor is row_width > 1, without a transposed copy.  num_segments x
+ * num_rows and row_width each fit 32 bits; their product may pass 2^32.  Ragged segments, exclusive and reverse scans, scans in place,
+ * logcumsumexp and complex dtypes are not offered.
+ * Ops and dtypes: VRS_SCAN_SUM and VRS_SCAN_PROD take int32, int64, float16, bfloat16, float32 or float64 into the same out_dtype, or
+ * int8, uint8, int16 or int32 into int64 (torch's default promotion, done by the load); float16 and bfloat16 are accumulated in float32
+ * and rounded once per output, to nearest even; integers wrap.  VRS_SCAN_MAX and VRS_SCAN_MIN take the nine dtypes of vrs_sort_dtype
+ * (out_dtype == dtype) and also write int64 row numbers into out_indices; they combine (value, row) pairs by torch's CPU rule: a NaN
+ * always replaces, a non-NaN replaces a non-NaN when it is >= (MIN: <=), so ties take the later row and its own bits, and after a NaN
+ * the row follows the latest NaN.  That combine is associative and exact: these two ops equal torch bit for bit.
+ * THE ORDER of sums and products is fixed: a function of (num_rows, row_width, dtype, op, T = VRS_TUNE_SCAN_TILE_ROWS) alone, never of
+ * timing, the grid, num_segments or where a segment lies, so the same input gives the same bits on every run; vrs_scan_rows_host
+ * evaluates the same functions on the host.  With F = 64 and every fold left to right from the op's identity (a float sum starts at
+ * +0.0, so cumsum([-0.0]) is +0.0):
+ *     A(0)_j = the aggregate of tile j (rows [jT, jT + T)) by the in-tile order;   A(k)_m = fold(A(k-1)_{mF} .. A(k-1)_{mF+F-1})
+ *     P_j    = fold of, for k from the top level down to 0, A(k)_m for m in [F * floor(j / F^(k+1)), floor(j / F^k))
+ *     out[i] = P_j (+) incl_j(i);   with num_rows <= T:  out[i] = incl_0(i)
+ * The in-tile order has two maps, written down in csrc/vrs_scan_order.hpp: the flat map (row_width == 1: chunks of 256 rows, four per
+ * lane, one six-step wave scan per chunk, the chunks in sequence) and the columns map (runs of 16 rows in sequence).
+ * Tiers (vrs_scan_tier_for): VRS_SCAN_TILE, num_rows <= T: one launch, one wave per segment (flat) or one lane per segment and column;
+ * VRS_SCAN_THREE_LAUNCH: an aggregates kernel, the carries (one small launch per level above the first, one for every P_j), an apply
+ * kernel -- every dtype, op and row_width, no waiting anywhere; VRS_SCAN_SINGLE_PASS: row_width == 1, SUM or PROD into int32, float16,
+ * bfloat16 or float32, from VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS rows per call on: one launch, tiles taken in order from a ticket, A(k)_m
+ * published in 64-bit status words that are their own flag, waiting bounded by VRS_TUNE_SCAN_SPIN_BUDGET polls, after which the waiting
+ * wave computes the missing word itself (the same bits).  All tiers give the same bits.
+ * scratch: at least vrs_scan_scratch_bytes(...) bytes for the context's tuning (0 for the tile tier: scratch may then be NULL), on a
+ * 16-byte boundary, contents afterwards unspecified.  values is never written; values, out, out_indices and scratch may not overlap.
+ * num_segments == 0 or num_rows == 0: VRS_OK, nothing done.  A NULL context, values, out, out_indices (MAX, MIN) or scratch (when
+ * needed), an unknown dtype / out_dtype / op triple, row_width == 0, num_segments x num_rows >= 2^32, undersized buffers and overlaps:
+ * VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Stream-ordered on the context's stream; the call only enqueues (after
+ * settling a pending one-call sort) and never waits for the device.
+ */
+typedef enum vrs_scan_op { VRS_SCAN_SUM = 0, VRS_SCAN_PROD = 1, VRS_SCAN_MAX = 2, VRS_SCAN_MIN = 3 } vrs_scan_op;
+typedef enum vrs_scan_tier { VRS_SCAN_TILE = 0, VRS_SCAN_THREE_LAUNCH = 1, VRS_SCAN_SINGLE_PASS = 2 } vrs_scan_tier;
+int vrs_scan_rows(vrs_context ctx, vrs_buffer values, uint32_t num_segments, uint32_t num_rows, uint32_t row_width, int dtype, int out_dtype,
+                  int op, vrs_buffer out, vrs_buffer out_indices /* MAX, MIN: int64, the shape of out; else NULL */, vrs_buffer scratch);
+/* the tier a call takes with tile_rows = VRS_TUNE_SCAN_TILE_ROWS (a multiple of 256 in 256 .. 8192) and single_pass_min_rows =
+ * VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS (0: never): a pure function, needs no device.  *tier = VRS_SCAN_*. */
+int vrs_scan_tier_for(uint32_t num_segments, uint32_t num_rows, uint32_t row_width, int dtype, int out_dtype, int op, uint32_t tile_rows,
+                      uint32_t single_pass_min_rows, int *tier);
+/* levels of aggregates a segment of num_rows rows takes: 0 up to tile_rows rows, 1 up to F tiles, one more per factor of F.  Pure. */
+int vrs_scan_levels_for(uint32_t num_rows, uint32_t tile_rows, uint32_t *levels);
+/* the longest chain of combines behind any output of a segment (combines with the identity counted): the factor of the rounding-error
+ * bound depth x u x cumsum(|x|), and at most tile_rows + F x (levels + 1).  Pure. */
+int vrs_scan_depth_for(uint32_t num_rows, uint32_t row_width, uint32_t tile_rows, uint32_t *depth);
+/* the scratch a call needs: a pure function, needs no device.  Three-launch: about 2 x a x row_width x num_segments x tiles bytes with
+ * a the accumulator's bytes (4, 8, or 16 for MAX and MIN); single pass: 256 + about 8 x num_segments x tiles. */
+int vrs_scan_scratch_bytes(uint32_t num_segments, uint32_t num_rows, uint32_t row_width, int dtype, int out_dtype, int op, uint32_t tile_rows,
+                           uint32_t single_pass_min_rows, uint64_t *bytes);
+/* vrs_scan_rows on the host, by the functions the kernels compile: host pointers, the same order, the same bits.  Needs no device. */
+int vrs_scan_rows_host(const void *values, uint32_t num_segments, uint32_t num_rows, uint32_t row_width, int dtype, int out_dtype, int op,
+                       uint32_t tile_rows, void *out, int64_t *out_indices);
+/* cumulative per context: calls per tier, and the status words a waiting wave of the single pass computed itself (waits for the
+ * context's stream; any pointer may be NULL) */
+int vrs_scan_stats(vrs_context ctx, uint64_t *tile_calls, uint64_t *three_launch_calls, uint64_t *single_pass_calls, uint64_t *takeovers);
+
+/*
  * Run-length encoding (build extension; no reference counterpart -- the reference's callers find each cell's or tile's [start, end)
  * in the sorted ids themselves): n keys of key_bytes (4 or 8) each, in any order, as maximal runs of bit-identical consecutive keys
  * (torch.unique_consecutive).  With R runs: out_keys[j] = the key of run j, out_offsets[j] = its first position and out_offsets[R] = n,
@@ -1031,6 +1090,14 @@ typedef enum vrs_tuning_key {
                                         skewed lists of 1- and 2-KB rows: a first setting (DESIGN "K13") */
     VRS_TUNE_REDUCE_LANE_ROWS = 36, /* segmented reduction, row_width < 64: chunks of up to this many rows (0 .. 64) are added by one lane per column.
                                        Default 16, not measured (DESIGN "K13") */
+    VRS_TUNE_SCAN_TILE_ROWS = 37, /* prefix scan: T, the rows of one tile (a multiple of 256 in 256 .. 8192).  Part of the order: another T, other
+                                     last bits of a float sum.  Default 2048, a first setting: in the one sweep taken (10^8 float32 along one row,
+                                     profiles/labs/k14_scan.txt) the single pass is fastest at 8192, the three-launch form alike at every T (DESIGN "K14") */
+    VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS = 38, /* prefix scan: the single pass runs from this many rows per call on where it applies; 0 = never.
+                                                Default 1048576, a first setting: at the one size measured (10^8 float32, profiles/labs/k14_scan.txt) the
+                                                single pass takes 0.37 ms against 0.26 ms for the three-launch form; other sizes are not measured (DESIGN "K14") */
+    VRS_TUNE_SCAN_SPIN_BUDGET = 39, /* prefix scan, single pass: polls of an unpublished status word (0 .. 1048576) before the waiting wave
+                                       computes it itself.  Default 4096, the run-length encode's; not measured (DESIGN "K14") */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

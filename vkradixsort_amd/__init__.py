@@ -13,6 +13,8 @@ binning    torch.bincount / torch.histc / torch.histogram drop-ins: counters in 
            (bincount, histc, histogram)
 reduce     torch.segment_reduce / index_add / index_reduce / scatter_reduce drop-ins with reproducible sums: a segmented reduction over
            rows in a fixed order (segment_reduce, index_add, index_reduce, scatter_reduce)
+scan       torch.cumsum / cumprod / cummax / cummin drop-ins: an inclusive prefix scan along any dim in a fixed order, the same bits on
+           every run (cumsum, cumprod, cummax, cummin)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
            for torch tensors)
 """
@@ -21,6 +23,7 @@ from .capi import PushConstants, VrsError, load_library  # noqa: F401
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
 from .reduce import index_add, index_reduce, reduce_stats, scatter_reduce, segment_reduce  # noqa: F401
+from .scan import cummax, cummin, cumprod, cumsum, scan_stats  # noqa: F401
 from .search import bucketize, search_stats, searchsorted  # noqa: F401
 from .segmented import segmented_stats, sort_rows, sort_segments  # noqa: F401
 from .selection import kthvalue, median, nanmedian, select_scratch_bytes, select_segments, select_stats  # noqa: F401

@@ -123,6 +123,12 @@ VRS_REDUCE_SUM, VRS_REDUCE_PROD, VRS_REDUCE_MIN, VRS_REDUCE_MAX = 0, 1, 2, 3
 VRS_REDUCE_MAP_LANE, VRS_REDUCE_MAP_ROWS, VRS_REDUCE_MAP_COLUMNS = 0, 1, 2
 VRS_TUNE_REDUCE_CHUNK_ROWS, VRS_TUNE_REDUCE_LANE_ROWS = 35, 36
 REDUCE_CHUNK_ROWS_DEFAULT, REDUCE_LANE_ROWS_DEFAULT = 512, 16
+# prefix scan over rows (vrs_scan_rows): ops, tiers (vrs_scan_tier), tuning keys, the library's defaults for them and the order's constants
+VRS_SCAN_SUM, VRS_SCAN_PROD, VRS_SCAN_MAX, VRS_SCAN_MIN = 0, 1, 2, 3
+VRS_SCAN_TILE, VRS_SCAN_THREE_LAUNCH, VRS_SCAN_SINGLE_PASS = 0, 1, 2
+VRS_TUNE_SCAN_TILE_ROWS, VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS, VRS_TUNE_SCAN_SPIN_BUDGET = 37, 38, 39
+SCAN_TILE_ROWS_DEFAULT, SCAN_SINGLE_PASS_MIN_ROWS_DEFAULT, SCAN_SPIN_BUDGET_DEFAULT = 2048, 1 << 20, 4096
+SCAN_TILE_ROWS_MIN, SCAN_TILE_ROWS_MAX, SCAN_FAN = 256, 8192, 64
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -283,6 +289,13 @@ _SIGNATURES = [
     ("vrs_segment_reduce_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
     ("vrs_segment_reduce_host", c_int, [c_void_p, c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_uint32, c_uint32, c_void_p]),
     ("vrs_segment_reduce_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_scan_rows", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vrs_scan_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_int)]),
+    ("vrs_scan_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
+    ("vrs_scan_depth_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_uint32)]),
+    ("vrs_scan_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_uint64)]),
+    ("vrs_scan_rows_host", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+    ("vrs_scan_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
     ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

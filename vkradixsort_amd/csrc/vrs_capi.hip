@@ -282,6 +282,7 @@ int vrs_context_destroy(vrs_context ctx) {
     topk_release(ctx);
     select_release(ctx);
     reduce_release(ctx);
+    scan_release(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return VRS_OK;
@@ -724,6 +725,18 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
         case VRS_TUNE_REDUCE_LANE_ROWS:
             if (value < 0 || value > 64) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the reduction's lane map takes 0 .. 64 rows");
             ctx->reduce_lane_rows = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_SCAN_TILE_ROWS:
+            if (value < 256 || value > 8192 || value % 256 != 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's tile must be a multiple of 256 in 256 .. 8192 rows");
+            ctx->scan_tile_rows = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS:
+            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's single pass starts at 0 (never) or more rows");
+            ctx->scan_single_pass_min_rows = static_cast<uint32_t>(value);
+            return VRS_OK;
+        case VRS_TUNE_SCAN_SPIN_BUDGET:
+            if (value < 0 || value > (1 << 20)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's spin budget must be 0 .. 1048576 polls");
+            ctx->scan_spin_budget = static_cast<uint32_t>(value);
             return VRS_OK;
         case VRS_TUNE_MSD_POOL_PAIRS_PACKED:
             if (value < -1 || value > 1) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pairs' packed local sort: -1 (by size), 0 (never) or 1 (always)");

@@ -189,6 +189,12 @@ struct vrs_context_t {
     vrs_reduce_state *reduce = nullptr;
     uint32_t reduce_chunk_rows = 512u;            // VRS_TUNE_REDUCE_CHUNK_ROWS
     uint32_t reduce_lane_rows = 16u;              // VRS_TUNE_REDUCE_LANE_ROWS
+    // prefix scan (vrs_capi_scan.hip); the defaults are vrs_scan_order.hpp's kScan*Default
+    uint32_t scan_tile_rows = 2048u;              // VRS_TUNE_SCAN_TILE_ROWS
+    uint32_t scan_single_pass_min_rows = 1u << 20;  // VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS
+    uint32_t scan_spin_budget = 4096u;            // VRS_TUNE_SCAN_SPIN_BUDGET
+    uint64_t scan_calls[3] = {};                  // calls per tier (vrs_scan_stats)
+    unsigned long long *scan_takeovers = nullptr; // device counter: words a waiting wave of the single pass computed itself
 };
 
 struct vrs_buffer_t {
@@ -325,6 +331,7 @@ void segmented_release(vrs_context ctx);
 void topk_release(vrs_context ctx);
 void select_release(vrs_context ctx);
 void reduce_release(vrs_context ctx);
+void scan_release(vrs_context ctx);
 
 // A context's cumulative device counters (count entries of T): made and zeroed on its stream at first use; read back once the calls
 // before have finished (all zeros when they were never made: counters == NULL).

@@ -698,6 +698,88 @@ int vrs_scan_rows_host(const void *values, uint32_t num_segments, uint32_t num_r
 int vrs_scan_stats(vrs_context ctx, uint64_t *tile_calls, uint64_t *three_launch_calls, uint64_t *single_pass_calls, uint64_t *takeovers);
 
 /*
+ * K15 -- ordered stream compaction (build extension; no reference counterpart): "keep the elements whose flag is nonzero, in input
+ * order, and say how many" -- torch.nonzero, argwhere, where(condition), masked_select, masked_scatter and count_nonzero.
+ * `flags`: n elements of `dtype`, one of the nine of vrs_sort_dtype or VRS_COMPACT_BOOL (one byte), read in their own width.  THE
+ * PREDICATE (csrc/vrs_compact_order.hpp, compiled by the kernels and by vrs_compact_host alike): an integer or bool is nonzero when its
+ * bits are; a float when its bits without the sign are -- so -0.0 is zero, and NaNs, infinities and subnormals are nonzero.
+ * The n elements are cut into tiles of T = VRS_TUNE_COMPACT_TILE_ELEMS elements.  Three phases, none of which polls, spins on or
+ * otherwise waits for memory another workgroup writes:
+ *   count    one workgroup per tile: 16-byte loads, the predicate's bits per lane, popcounts; one uint32 per tile into scratch
+ *   carries  one workgroup: the exclusive scan of the tiles' counts in place, 4096 of them per step; the total R as a uint64
+ *   emit     one workgroup per tile: the flags again, every survivor's rank in input order, the survivors of 4096 elements staged in LDS
+ *            and written as dense runs in output order; a tile without survivors is not read again
+ * vrs_compact_count enqueues count and carries; vrs_compact_emit enqueues emit against the offsets that call left in `scratch`.  THE
+ * CONTRACT between the two: the same flags (unchanged), the same n and dtype, the same scratch, the same VRS_TUNE_COMPACT_TILE_ELEMS,
+ * and no other compact call on that scratch in between.  Several emit calls may follow one count call.  outputs->num_selected is R as
+ * the count call reported it: it sizes the checks of the output buffers, it is the leading dimension of the column layout, and whatever
+ * `scratch` holds, no output row from num_selected on is written and no source element from there on is read.
+ * Outputs of emit, in any combination (a NULL handle leaves one out):
+ *   flat            R int64: the survivors' positions
+ *   coords          R x ndim int64: their coordinates in a contiguous array of shape[0 .. ndim) (1 .. 8 sizes whose product is n), as
+ *                   rows [R, ndim] (VRS_COMPACT_ROWS, torch.nonzero) or as columns [ndim, R] (VRS_COMPACT_COLUMNS, as_tuple=True)
+ *   gather_out      R elements of value_bytes (1, 2, 4 or 8): gather_values[position], copied as bits (masked_select)
+ *   scatter_out     n elements of value_bytes: out[i] = flag[i] ? scatter_source[rank(i)] : scatter_input[i], rank(i) the nonzero flags
+ *                   in front of i (masked_scatter); scatter_source holds at least R elements, what lies behind R is never read
+ * n < 2^32.  flags on its element's boundary (16-byte loads are used when it starts on a 16-byte boundary), scratch on a 16-byte
+ * boundary and at least vrs_compact_scratch_bytes(n, T) bytes, value buffers on their element's boundary, int64 outputs on 8 bytes.
+ * n == 0: VRS_OK, nothing enqueued but the count itself (0).  A NULL context, flags or scratch, an unknown dtype, layout or value_bytes,
+ * ndim outside 1 .. 8, a shape whose product is not n, undersized buffers and an output that overlaps flags or scratch:
+ * VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Stream-ordered on the context's stream; the calls only enqueue (after
+ * settling a pending one-call sort), except that vrs_compact_count with host_count waits for the stream: the one host read torch's
+ * own nonzero makes too.
+ */
+#define VRS_COMPACT_BOOL 9 /* after the nine of vrs_sort_dtype */
+typedef enum vrs_compact_layout { VRS_COMPACT_ROWS = 0, VRS_COMPACT_COLUMNS = 1 } vrs_compact_layout;
+typedef struct vrs_compact_outputs {
+    uint64_t num_selected;     /* R, as vrs_compact_count reported it */
+    vrs_buffer flat;           /* NULL, or R int64 */
+    vrs_buffer coords;         /* NULL, or R x ndim int64 */
+    int coords_layout;         /* VRS_COMPACT_ROWS or VRS_COMPACT_COLUMNS */
+    uint32_t ndim;             /* with coords: 1 .. 8 */
+    uint32_t shape[8];         /* with coords: sizes whose product is n */
+    vrs_buffer gather_values;  /* with gather_out: n elements of value_bytes */
+    vrs_buffer gather_out;     /* NULL, or R elements of value_bytes */
+    uint32_t value_bytes;      /* of gather_* and scatter_*: 1, 2, 4 or 8 */
+    uint32_t reserved;         /* 0 */
+    vrs_buffer scatter_input;  /* with scatter_out: n elements */
+    vrs_buffer scatter_source; /* with scatter_out: at least R elements (may be NULL when R is 0) */
+    vrs_buffer scatter_out;    /* NULL, or n elements */
+} vrs_compact_outputs;
+/* count and carries.  out_count_device: NULL, or 8 bytes that receive R as an int64 on the device; host_count: NULL, or where R goes
+ * once the stream has been waited for. */
+int vrs_compact_count(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, vrs_buffer scratch, vrs_buffer out_count_device, uint64_t *host_count);
+int vrs_compact_emit(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, vrs_buffer scratch, const vrs_compact_outputs *outputs);
+/* tiles of tile_elems (a multiple of 4096 in 4096 .. 65536) that cover n < 2^32 elements, and the scratch they take (256 bytes and 4 per
+ * tile, rounded up to 256): pure functions, need no device */
+int vrs_compact_tiles_for(uint64_t n, uint32_t tile_elems, uint32_t *tiles);
+int vrs_compact_scratch_bytes(uint64_t n, uint32_t tile_elems, uint64_t *bytes);
+/* the quotient and remainder of a 32-bit numerator by divisor >= 1 as the kernels form them (a multiplication by a constant made from
+ * the divisor): pure, needs no device */
+int vrs_compact_divide(uint32_t numerator, uint32_t divisor, uint32_t *quotient, uint32_t *remainder);
+/* the same predicate, order and coordinate arithmetic on host pointers, by the functions the kernels compile.  Needs no device.  Every
+ * output may be NULL; out_flat, out_coords and gather_out have room for every survivor (at most n); scatter_source holds
+ * scatter_source_elems elements, of which the first R are read: fewer than R is VRS_ERROR_INVALID_ARGUMENT with nothing written to
+ * scatter_out.  *out_count = R. */
+typedef struct vrs_compact_host_outputs {
+    int64_t *flat;
+    int64_t *coords;
+    int coords_layout;
+    uint32_t ndim;
+    uint32_t shape[8];
+    const void *gather_values;
+    void *gather_out;
+    uint32_t value_bytes;
+    uint32_t reserved;
+    const void *scatter_input, *scatter_source;
+    uint64_t scatter_source_elems;
+    void *scatter_out;
+} vrs_compact_host_outputs;
+int vrs_compact_host(const void *flags, uint64_t n, int dtype, const vrs_compact_host_outputs *outputs, uint64_t *out_count);
+/* cumulative per context: count calls, emit calls and the elements the count calls were given (any pointer may be NULL) */
+int vrs_compact_stats(vrs_context ctx, uint64_t *count_calls, uint64_t *emit_calls, uint64_t *elements);
+
+/*
  * Run-length encoding (build extension; no reference counterpart -- the reference's callers find each cell's or tile's [start, end)
  * in the sorted ids themselves): n keys of key_bytes (4 or 8) each, in any order, as maximal runs of bit-identical consecutive keys
  * (torch.unique_consecutive).  With R runs: out_keys[j] = the key of run j, out_offsets[j] = its first position and out_offsets[R] = n,
@@ -1098,6 +1180,9 @@ typedef enum vrs_tuning_key {
                                                 single pass takes 0.37 ms against 0.26 ms for the three-launch form; other sizes are not measured (DESIGN "K14") */
     VRS_TUNE_SCAN_SPIN_BUDGET = 39, /* prefix scan, single pass: polls of an unpublished status word (0 .. 1048576) before the waiting wave
                                        computes it itself.  Default 4096, the run-length encode's; not measured (DESIGN "K14") */
+    VRS_TUNE_COMPACT_TILE_ELEMS = 40, /* compaction: T, the elements of one tile (a multiple of 4096 in 4096 .. 65536): one uint32 of scratch and one
+                                         workgroup of each phase per tile.  Default 16384, a first setting: the one sweep taken (10^8 bool flags,
+                                         profiles/labs/k15_compact.txt) is flat from 8192 to 65536 (DESIGN "K15") */
     VRS_TUNE_DEBUG_POOL_NO_MEMORY = 25, /* test hook: the next `value` allocations of the pool form's scratch fail as if the device were full */
     VRS_TUNE_DEBUG_XCC_ROTATE = 21, /* test hook: run the placement probe again and rotate its result by `value` places (0 .. 7), as if the probe had
                                        run on another hardware queue than the sorts do (the dispatcher starts every queue's round-robin at its

@@ -15,11 +15,16 @@ reduce     torch.segment_reduce / index_add / index_reduce / scatter_reduce drop
            rows in a fixed order (segment_reduce, index_add, index_reduce, scatter_reduce)
 scan       torch.cumsum / cumprod / cummax / cummin drop-ins: an inclusive prefix scan along any dim in a fixed order, the same bits on
            every run (cumsum, cumprod, cummax, cummin)
+compact    torch.nonzero / argwhere / where(condition) / count_nonzero / masked_select / masked_scatter drop-ins: ordered stream compaction
+           in three phases that wait nowhere -- count, carries, emit (nonzero, argwhere, where, count_nonzero, masked_select,
+           masked_scatter)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
            for torch tensors)
 """
 from .binning import bincount, bincount_stats, histc, histogram  # noqa: F401
 from .capi import PushConstants, VrsError, load_library  # noqa: F401
+from .compact import (argwhere, compact_stats, count_nonzero, masked_scatter, masked_select, nonzero,  # noqa: F401
+                      where)
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
 from .reduce import index_add, index_reduce, reduce_stats, scatter_reduce, segment_reduce  # noqa: F401

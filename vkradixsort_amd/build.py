@@ -23,7 +23,8 @@ HIP_SOURCES = [CSRC / name for name in ("vrs_contract.hip", "vrs_one_call.hip", 
                                         "vrs_unique.hip", "vrs_capi_unique.hip", "vrs_sort_rank.hip", "vrs_capi_sort_rank.hip",
                                         "vrs_search.hip", "vrs_capi_search.hip", "vrs_bincount.hip", "vrs_capi_bincount.hip",
                                         "vrs_segreduce.hip", "vrs_capi_segreduce.hip",
-                                        "vrs_scan.hip", "vrs_scan_pairs.hip", "vrs_capi_scan.hip")]
+                                        "vrs_scan.hip", "vrs_scan_pairs.hip", "vrs_capi_scan.hip",
+                                        "vrs_compact.hip", "vrs_capi_compact.hip")]
 HIP_HEADERS = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + [INCLUDE / "vkradixsort_amd.h"]  # every object is rebuilt when any header is newer
 ARCH = "gfx950"
 

@@ -129,6 +129,13 @@ VRS_SCAN_TILE, VRS_SCAN_THREE_LAUNCH, VRS_SCAN_SINGLE_PASS = 0, 1, 2
 VRS_TUNE_SCAN_TILE_ROWS, VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS, VRS_TUNE_SCAN_SPIN_BUDGET = 37, 38, 39
 SCAN_TILE_ROWS_DEFAULT, SCAN_SINGLE_PASS_MIN_ROWS_DEFAULT, SCAN_SPIN_BUDGET_DEFAULT = 2048, 1 << 20, 4096
 SCAN_TILE_ROWS_MIN, SCAN_TILE_ROWS_MAX, SCAN_FAN = 256, 8192, 64
+# ordered compaction (vrs_compact_*): bool's dtype code after the nine of vrs_sort_dtype, the coordinate layouts, the tuning key, its
+# default and range, and the constants of the phases (a chunk is what one step of emit stages in LDS; the carries take a block per step)
+VRS_COMPACT_BOOL = 9
+VRS_COMPACT_ROWS, VRS_COMPACT_COLUMNS = 0, 1
+VRS_TUNE_COMPACT_TILE_ELEMS = 40
+COMPACT_TILE_ELEMS_DEFAULT, COMPACT_TILE_ELEMS_MIN, COMPACT_TILE_ELEMS_MAX = 16384, 4096, 65536
+COMPACT_CHUNK, COMPACT_CARRY_BLOCK, COMPACT_MAX_DIMS = 4096, 4096, 8
 FORM_NAMES = {0: "none", 1: "single", 2: "contract", 3: "lsd", 4: "counted", 5: "pool"}
 FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_min_keys", "hybrid", "pool", "pool_pairs", "reserve", "groups", "xcc_map_valid",
               "atomic_rank", "pool_skip", "pool_skip_n", "wide_refused", "wide_skipped", "no_pool", "no_hybrid"]
@@ -157,6 +164,20 @@ class DistTransport(ctypes.Structure):
     """vrs_dist_transport: the wire of the multi-GPU step as a table of functions (include/vkradixsort_amd.h)."""
     _fields_ = [("user", c_void_p), ("all_gather", c_void_p), ("all_reduce", c_void_p), ("group_start", c_void_p),
                 ("send", c_void_p), ("recv", c_void_p), ("group_end", c_void_p), ("error_string", c_void_p)]
+
+
+class CompactOutputs(ctypes.Structure):
+    """vrs_compact_outputs: what vrs_compact_emit writes (include/vkradixsort_amd.h "K15")."""
+    _fields_ = [("num_selected", c_uint64), ("flat", c_void_p), ("coords", c_void_p), ("coords_layout", c_int), ("ndim", c_uint32),
+                ("shape", c_uint32 * 8), ("gather_values", c_void_p), ("gather_out", c_void_p), ("value_bytes", c_uint32),
+                ("reserved", c_uint32), ("scatter_input", c_void_p), ("scatter_source", c_void_p), ("scatter_out", c_void_p)]
+
+
+class CompactHostOutputs(ctypes.Structure):
+    """vrs_compact_host_outputs: the same on host pointers, for vrs_compact_host."""
+    _fields_ = [("flat", c_void_p), ("coords", c_void_p), ("coords_layout", c_int), ("ndim", c_uint32), ("shape", c_uint32 * 8),
+                ("gather_values", c_void_p), ("gather_out", c_void_p), ("value_bytes", c_uint32), ("reserved", c_uint32),
+                ("scatter_input", c_void_p), ("scatter_source", c_void_p), ("scatter_source_elems", c_uint64), ("scatter_out", c_void_p)]
 
 
 MSD_COUNT_WORDS = 16384 + 8 * 256 + 64
@@ -296,6 +317,13 @@ _SIGNATURES = [
     ("vrs_scan_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_uint64)]),
     ("vrs_scan_rows_host", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p]),
     ("vrs_scan_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_compact_count", c_int, [c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("vrs_compact_emit", c_int, [c_void_p, c_void_p, c_uint64, c_int, c_void_p, POINTER(CompactOutputs)]),
+    ("vrs_compact_tiles_for", c_int, [c_uint64, c_uint32, POINTER(c_uint32)]),
+    ("vrs_compact_scratch_bytes", c_int, [c_uint64, c_uint32, POINTER(c_uint64)]),
+    ("vrs_compact_divide", c_int, [c_uint32, c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
+    ("vrs_compact_host", c_int, [c_void_p, c_uint64, c_int, POINTER(CompactHostOutputs), POINTER(c_uint64)]),
+    ("vrs_compact_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
     ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

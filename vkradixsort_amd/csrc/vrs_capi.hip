@@ -738,6 +738,11 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
             if (value < 0 || value > (1 << 20)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's spin budget must be 0 .. 1048576 polls");
             ctx->scan_spin_budget = static_cast<uint32_t>(value);
             return VRS_OK;
+        case VRS_TUNE_COMPACT_TILE_ELEMS:
+            if (value < 4096 || value > 65536 || value % 4096 != 0)
+                return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the compaction's tile must be a multiple of 4096 in 4096 .. 65536 elements");
+            ctx->compact_tile_elems = static_cast<uint32_t>(value);
+            return VRS_OK;
         case VRS_TUNE_MSD_POOL_PAIRS_PACKED:
             if (value < -1 || value > 1) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pairs' packed local sort: -1 (by size), 0 (never) or 1 (always)");
             ctx->os_pool_pairs_packed = value;

@@ -195,6 +195,10 @@ struct vrs_context_t {
     uint32_t scan_spin_budget = 4096u;            // VRS_TUNE_SCAN_SPIN_BUDGET
     uint64_t scan_calls[3] = {};                  // calls per tier (vrs_scan_stats)
     unsigned long long *scan_takeovers = nullptr; // device counter: words a waiting wave of the single pass computed itself
+    // ordered compaction (vrs_capi_compact.hip); the default is vrs_compact_order.hpp's kCompactTileDefault
+    uint32_t compact_tile_elems = 16384u;         // VRS_TUNE_COMPACT_TILE_ELEMS
+    uint64_t compact_calls[2] = {};               // count calls, emit calls (vrs_compact_stats)
+    uint64_t compact_elements = 0;                // elements the count calls were given
 };
 
 struct vrs_buffer_t {

@@ -469,6 +469,72 @@ int vrs_select_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_se
                      uint64_t *compacted_segments);
 
 /*
+ * Multi-rank selection (build extension; no reference counterpart): torch.quantile / torch.nanquantile -- for every segment and every q
+ * the two neighbouring entries of the segment's ascending order, the weight between them and the interpolated quantile, by a radix
+ * select that carries every target through one sequence of reads.  src: num_elements elements of `dtype` (VRS_SORT_F32 or VRS_SORT_F64,
+ * as torch); offsets: a device buffer of num_segments + 1 uint32; segment i is src[offsets[i], offsets[i+1]) clamped exactly as
+ * vrs_select_segments clamps it, L its length; a segment may begin at any element.  q: num_q doubles on the host, each in [0, 1] (they
+ * are copied before the call returns).  flags: VRS_QUANTILE_IGNORE_NAN gives the nanquantile rule.
+ * Outputs: [num_segments, num_q] elements of `dtype` each; out_values the quantile; out_lower, out_upper and out_weight (each may be NULL)
+ * the two order statistics and the weight.  A segment with no answer -- L == 0, any NaN without the flag, NaNs alone with it -- gets the
+ * quiet NaN in all four.  The rule (vrs_quantile_target_for; T the dtype, nans the segment's NaNs, counted by the first read):
+ *   L' = L, or L - nans with the flag;  r = T(q) * T(L' - 1), one rounded multiply;  LOWER / HIGHER / NEAREST: r = floor / ceil /
+ *   round-half-even of r;  lower = floor(r), upper = ceil(r), both clamped to L' - 1 (T(L' - 1) rounds up past the last index for float32
+ *   segments longer than 2^24);  weight = r - floor(r), 0.5 for MIDPOINT, 0 for the three single-entry modes;
+ *   value = weight < 0.5 ? a + weight * (b - a) : b - (b - a) * (1 - weight) for LINEAR and MIDPOINT (a, b the two entries' values; every
+ *   operation rounded on its own, the same bits on the host and on the device; a NaN result is the quiet NaN), a for the rest.
+ * The entries' values are rebuilt from their ranks: +0.0 for either zero (the NaN class is never an entry).
+ * The selection: per segment the distinct entries asked for, ascending, 16 at the most (VRS_QUANTILE_MAX_TARGETS: num_q * 2 for LINEAR
+ * and MIDPOINT, num_q for the rest, must not exceed it).  Levels as vrs_quantile_level_for gives them: the top 11 bits of the rank in one
+ * histogram over every key, then 8 bits at a time (the last level: what is left; 4 levels for float32, 8 for float64) in one 256-bin
+ * histogram per group of targets that share their prefix so far -- one read of its source per level, whatever the number of targets.
+ * Tiers by clamped length exactly as vrs_select_tier_for decides them (the same VRS_TUNE_SELECT_GRID_MIN_KEYS): LDS, BLOCK and GRID; in
+ * the GRID tier, after a level whose live groups together hold at most L / VRS_TUNE_SELECT_COMPACT_DIVISOR keys (and at most 1024 per
+ * 16384 keys of the segment), with two levels or more still to come, the ranks of those keys are copied once into the scratch buffer,
+ * where the later levels read them.
+ * scratch: at least vrs_quantile_scratch_bytes(...) bytes on an 8-byte boundary, contents afterwards unspecified; given that much the
+ * call never fails for lack of memory.  num_segments == 0 or num_q == 0: VRS_OK, nothing done.  Another dtype, an unknown interpolation
+ * or flag bit, a q outside [0, 1] or NaN, more targets than VRS_QUANTILE_MAX_TARGETS, a NULL context, src, offsets, out_values or
+ * scratch, undersized buffers and float64 off an 8-byte boundary: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
+ * Stream-ordered on the context's stream; the call only enqueues (after settling a pending one-call sort) and never waits for the device.
+ */
+typedef enum vrs_quantile_interpolation {
+    VRS_QUANTILE_LINEAR = 0,
+    VRS_QUANTILE_LOWER = 1,
+    VRS_QUANTILE_HIGHER = 2,
+    VRS_QUANTILE_MIDPOINT = 3,
+    VRS_QUANTILE_NEAREST = 4
+} vrs_quantile_interpolation;
+enum { VRS_QUANTILE_IGNORE_NAN = 1 }; /* flags */
+enum { VRS_QUANTILE_MAX_TARGETS = 16 };
+int vrs_quantile_segments(vrs_context ctx, vrs_buffer src, uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments,
+                          int dtype /* VRS_SORT_F32 or VRS_SORT_F64 */, const double *q, uint32_t num_q, int interpolation, int flags,
+                          vrs_buffer out_values, vrs_buffer out_lower /* may be NULL */, vrs_buffer out_upper /* may be NULL */,
+                          vrs_buffer out_weight /* may be NULL */, vrs_buffer scratch);
+/* the scratch vrs_quantile_segments needs: a pure function, needs no device.  0 for num_segments == 0; never shrinks as an argument grows:
+ * 16 KiB of histograms and 512 bytes of state per grid slot (num_elements / 8193 slots, 4096 at the most), 4 bytes per segment, and
+ * 1024 ranks per 16384 elements. */
+int vrs_quantile_scratch_bytes(uint32_t num_elements, uint32_t num_segments, int dtype, uint64_t *bytes);
+/* the rule both the device and the tests use for the entries a q asks for (above): a pure function, needs no device.  *weight: the
+ * dtype's weight, widened.  *valid = 0: the segment has no answer (*lower = *upper = 0).  Refuses what vrs_quantile_segments refuses,
+ * and nans > len. */
+int vrs_quantile_target_for(int dtype, int interpolation, double q, uint32_t len, uint32_t nans, int ignore_nan, uint32_t *lower,
+                            uint32_t *upper, double *weight, int *valid);
+/* the level table of a rank of `bits` bits (32 or 64): *levels, and the digit of level `level` (0 = the top one) as rank >> *shift &
+ * *mask.  32: 11, 8, 8, 5 bits; 64: 11, 8 x 6, 5.  A pure function, needs no device. */
+int vrs_quantile_level_for(int bits, int level, uint32_t *shift, uint32_t *mask, int *levels);
+/* vrs_quantile_segments evaluated on the host, every pointer in host memory: each segment's ranks sorted, then the same rule and the same
+ * interpolation.  The device's outputs equal these bit for bit.  Refuses what vrs_quantile_segments refuses. */
+int vrs_quantile_host(const void *src, uint32_t num_elements, const uint32_t *offsets, uint32_t num_segments, int dtype, const double *q,
+                      uint32_t num_q, int interpolation, int flags, void *out_values, void *out_lower /* may be NULL */,
+                      void *out_upper /* may be NULL */, void *out_weight /* may be NULL */);
+/* cumulative per context, this call's own counters: segments each tier was given by the classification, and grid-tier segments that
+ * sieved (waits for the context's stream; any pointer may be NULL).  Grid-tier segments beyond the scratch buffer's slots count as grid
+ * and run in the BLOCK kernel. */
+int vrs_quantile_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segments, uint64_t *grid_segments,
+                       uint64_t *sieved_segments);
+
+/*
  * Sorted-sequence search (build extension; no reference counterpart): torch.searchsorted / torch.bucketize / numpy.searchsorted.
  * `boundaries`: num_boundaries elements of `dtype` (a vrs_sort_dtype) as rows of boundary_row_len, each ascending in r; `queries`:
  * num_queries elements of the same dtype as rows of query_row_len.  Either there is exactly one boundary row, which every query
@@ -1164,10 +1230,12 @@ typedef enum vrs_tuning_key {
                                        workgroups per CU): a first setting, not a measured one (DESIGN "K11") */
     VRS_TUNE_SELECT_GRID_MIN_KEYS = 33, /* one-rank selection: segments of this many keys or more take the grid tier (every phase one launch
                                          over all of them); 0 = never.  Default 2^17: top-k's measured crossover for the same walk shape,
-                                         a first setting, not measured for this kernel (DESIGN "K12") */
+                                         a first setting, not measured for this kernel (DESIGN "K12").  vrs_quantile_segments reads it
+                                         too: its tiers are the same cuts (DESIGN "K16") */
     VRS_TUNE_SELECT_COMPACT_DIVISOR = 34, /* one-rank selection, grid tier: after a level whose chosen bin holds at most length / value keys
                                          (and at most 1024 per 16384 keys of the segment, what its area holds) the matching keys' ranks are
-                                         copied once and the later levels read the copy; 0 = never.  Default 16, not measured (DESIGN "K12") */
+                                         copied once and the later levels read the copy; 0 = never.  Default 16, not measured (DESIGN "K12").
+                                         vrs_quantile_segments reads it too: there the keys of all live groups together count (DESIGN "K16") */
     VRS_TUNE_REDUCE_CHUNK_ROWS = 35, /* segmented reduction: CH, the rows of one chunk (64 .. 4096).  Default 512, a split length known to even out
                                         skewed lists of 1- and 2-KB rows: a first setting (DESIGN "K13") */
     VRS_TUNE_REDUCE_LANE_ROWS = 36, /* segmented reduction, row_width < 64: chunks of up to this many rows (0 .. 64) are added by one lane per column.

@@ -7,6 +7,8 @@ segmented  many independent segments sorted in one call (sort_segments over Buff
 topk       the k smallest / largest keys of every segment by radix select (topk_segments over Buffers, topk for torch tensors)
 selection  torch.kthvalue / torch.median / torch.nanmedian drop-ins by a one-rank radix select: nine dtypes, any dim (select_segments over
            Buffers; kthvalue, median, nanmedian for torch tensors)
+quantile   torch.quantile / torch.nanquantile drop-ins by a multi-rank radix select: up to 16 order statistics per row carried through one
+           sequence of reads, values only (quantile_segments over Buffers; quantile, nanquantile for torch tensors)
 sort       torch.sort / torch.argsort drop-ins: any dim, descending, nine dtypes, torch's order bit for bit (sort, sort_values, argsort)
 search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize)
 binning    torch.bincount / torch.histc / torch.histogram drop-ins: counters in LDS or global memory, integer counts converted once
@@ -27,6 +29,7 @@ from .compact import (argwhere, compact_stats, count_nonzero, masked_scatter, ma
                       where)
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
+from .quantile import nanquantile, quantile, quantile_scratch_bytes, quantile_segments, quantile_stats  # noqa: F401
 from .reduce import index_add, index_reduce, reduce_stats, scatter_reduce, segment_reduce  # noqa: F401
 from .scan import cummax, cummin, cumprod, cumsum, scan_stats  # noqa: F401
 from .search import bucketize, search_stats, searchsorted  # noqa: F401

@@ -94,6 +94,10 @@ VRS_SELECT_LDS, VRS_SELECT_BLOCK, VRS_SELECT_GRID = 0, 1, 2
 SELECT_LDS_BYTES = 32 * 1024
 VRS_TUNE_SELECT_GRID_MIN_KEYS, VRS_TUNE_SELECT_COMPACT_DIVISOR = 33, 34
 SELECT_GRID_MIN_KEYS_DEFAULT, SELECT_COMPACT_DIVISOR_DEFAULT = 1 << 17, 16
+# multi-rank selection (vrs_quantile_segments): interpolations, the flag, the most targets per segment (its tiers and tuning keys are the selection's)
+VRS_QUANTILE_LINEAR, VRS_QUANTILE_LOWER, VRS_QUANTILE_HIGHER, VRS_QUANTILE_MIDPOINT, VRS_QUANTILE_NEAREST = 0, 1, 2, 3, 4
+VRS_QUANTILE_IGNORE_NAN = 1
+VRS_QUANTILE_MAX_TARGETS = 16
 # run-length encoding and unique: scratch flags, key types, and the encode's tile (keys per look-back status word)
 VRS_RLE_COUNTS = 1
 VRS_UNIQUE_U32, VRS_UNIQUE_I32, VRS_UNIQUE_F32, VRS_UNIQUE_U64, VRS_UNIQUE_I64, VRS_UNIQUE_F64 = 0, 1, 2, 3, 4, 5
@@ -292,6 +296,13 @@ _SIGNATURES = [
     ("vrs_select_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
     ("vrs_select_target_for", c_int, [c_int, c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_int)]),
     ("vrs_select_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("vrs_quantile_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, POINTER(c_double), c_uint32, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    ("vrs_quantile_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+    ("vrs_quantile_target_for", c_int, [c_int, c_int, c_double, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_double), POINTER(c_int)]),
+    ("vrs_quantile_level_for", c_int, [c_int, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
+    ("vrs_quantile_host", c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_int, POINTER(c_double), c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vrs_quantile_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("vrs_search_sorted", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     ("vrs_search_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
     ("vrs_search_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, c_int, c_int, POINTER(c_uint64)]),

@@ -281,6 +281,7 @@ int vrs_context_destroy(vrs_context ctx) {
     segmented_release(ctx);
     topk_release(ctx);
     select_release(ctx);
+    quantile_release(ctx);
     reduce_release(ctx);
     scan_release(ctx);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);

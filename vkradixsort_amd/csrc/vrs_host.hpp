@@ -177,6 +177,8 @@ struct vrs_context_t {
     vrs_select_state *select = nullptr;
     uint32_t select_grid_min_keys = 1u << 17;  // VRS_TUNE_SELECT_GRID_MIN_KEYS
     uint32_t select_compact_divisor = 16u;     // VRS_TUNE_SELECT_COMPACT_DIVISOR
+    // multi-rank selection (vrs_capi_quantile.hip): reads the two settings above; its own device counters
+    unsigned long long *quantile_stats = nullptr;  // [4] cumulative segments per tier and grid slots that sieved
     // sorted-sequence search (vrs_capi_search.hip); the defaults are vrs_search.hpp's kSearchDefault*
     uint32_t search_lds_bytes = 64u * 1024u;      // VRS_TUNE_SEARCH_LDS_BYTES
     uint32_t search_table_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_TABLE_MIN_QUERIES
@@ -334,6 +336,7 @@ int settle_pending(vrs_context ctx);
 void segmented_release(vrs_context ctx);
 void topk_release(vrs_context ctx);
 void select_release(vrs_context ctx);
+void quantile_release(vrs_context ctx);
 void reduce_release(vrs_context ctx);
 void scan_release(vrs_context ctx);
 

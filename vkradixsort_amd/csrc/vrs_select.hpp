@@ -12,6 +12,7 @@ namespace vrs {
 constexpr uint32_t kSelLdsBytes = 32768u;                  // the LDS tier's ranks: 8192 of up to 4 bytes, 4096 of 8 bytes
 constexpr uint32_t kSelDefaultGridMinKeys = 1u << 17;      // VRS_TUNE_SELECT_GRID_MIN_KEYS default: top-k's crossover, not measured here (DESIGN "K12")
 constexpr uint32_t kSelDefaultCompactDivisor = 16u;        // VRS_TUNE_SELECT_COMPACT_DIVISOR default (not measured either)
+// (the multi-rank selection, vrs_quantile.hpp, reads both keys too: the same tiers, and its sieve counts the keys of all live groups)
 constexpr uint32_t kSelAreaPerTile = kTopkTile / 16u;      // ranks of the compacted area per 16384-key tile of a grid slot
 constexpr uint32_t kSelSlotFloor = 8192u;                  // a grid slot is longer than this whatever the width: n / 8193 slots at the most
 constexpr int kSelKth = 0, kSelMedian = 1, kSelNanMedian = 2;  // vrs_select_mode

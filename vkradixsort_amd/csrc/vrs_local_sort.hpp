@@ -30,6 +30,9 @@ __device__ __forceinline__ void store_sorted(uint4 *p, const uint4 &q) {
 
 // k[4 j + c] = slot 4 (j STRIDE + t) + c of src, for the slots [0, words): a bucket as rows of 16-byte vectors, the way both bodies below
 // take it.  t: the thread's index in its row -- threadIdx.x for a workgroup, threadIdx.x & 63 for a wave.
+// The rows are asked for in the order they are used (rows_in_order): left to itself the scheduler issued row 0 fifth of six and third of
+// four, and the skew check -- which looks at row 0 alone -- and pass 1 then waited for nearly the whole bucket before their first instruction.
+__device__ __forceinline__ void rows_in_order() { __builtin_amdgcn_sched_barrier(0); }
 template <int STRIDE, int VEC>
 __device__ __forceinline__ void load_rows(uint32_t (&k)[4 * VEC], const uint32_t *src, uint32_t words, uint32_t t) {
     const uint32_t nvec = (words + 3u) / 4u;
@@ -38,11 +41,47 @@ __device__ __forceinline__ void load_rows(uint32_t (&k)[4 * VEC], const uint32_t
         uint32_t v = j * STRIDE + t;
         if (j == VEC - 1) v = v < nvec ? v : nvec - 1u;  // only the last row can reach behind the bucket
         const uint4 q = reinterpret_cast<const uint4 *>(src)[v];
+        if (j + 1 < VEC) rows_in_order();
         k[4 * j] = q.x;
         k[4 * j + 1] = q.y;
         k[4 * j + 2] = q.z;
         k[4 * j + 3] = q.w;
     }
+}
+
+// Inclusive prefix sum of x over the wave's 64 lanes, by data-parallel-primitive moves between registers: four shifts inside each row of 16
+// lanes, then lane 15 of a row to the row above and lane 31 to the upper half.  __shfl_up does the same sum through the LDS crossbar -- six
+// ds_bpermute round trips, each waited for, in a kernel whose LDS pipe is what it waits for.
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
+    x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xf, 0xf, false);  // row_shr:1 (a lane without a source adds 0)
+    x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xf, 0xf, false);  // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xf, 0xf, false);  // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xf, 0xf, false);  // row_shr:8
+    x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+    x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+    return x;
+}
+
+// x exists in a register from here on, as far as the optimiser can tell: what was computed into it is not computed later or under a branch
+__device__ __forceinline__ void pinned(uint32_t &x) { asm volatile("" : "+v"(x)); }
+
+// s_tmp[0] + .. + s_tmp[wave - 1] of the WAVES (4, 8 or 16) per-wave totals a scan left at s_tmp (16-byte aligned): whole 16-byte reads and
+// selects in registers (written `acc += v < wave ? s_tmp[v] : 0`, the compiler emits one read and one wait per v)
+template <int WAVES>
+__device__ __forceinline__ uint32_t waves_before(const uint32_t *s_tmp, uint32_t wave) {
+    static_assert(WAVES % 4 == 0, "whole 16-byte vectors");
+    uint4 t[WAVES / 4];
+#pragma unroll
+    for (int g = 0; g < WAVES / 4; ++g) t[g] = reinterpret_cast<const uint4 *>(s_tmp)[g];
+    uint32_t sum = 0;
+#pragma unroll
+    for (int g = 0; g < WAVES / 4; ++g) {
+        sum += (4u * g + 0u < wave) ? t[g].x : 0u;
+        sum += (4u * g + 1u < wave) ? t[g].y : 0u;
+        sum += (4u * g + 2u < wave) ? t[g].z : 0u;
+        sum += (4u * g + 3u < wave) ? t[g].w : 0u;
+    }
+    return sum;
 }
 
 // ALIGNED_IN: mis_in == 0 (a bucket read from its own 16-byte aligned region, written elsewhere): the slots without a key are then
@@ -90,17 +129,10 @@ __device__ __forceinline__ void lean_sort_body(uint32_t (&k)[4 * VEC], uint32_t 
             c[0] = s_hist[tid];
             total = c[0];
         }
-        uint32_t incl = total;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o);
-            if (lane >= static_cast<uint32_t>(o)) incl += t;
-        }
+        const uint32_t incl = wave_inclusive_sum(total);
         if (lane == 63u) s_tmp[wave] = incl;
         __syncthreads();
-        uint32_t acc = incl - total;
-#pragma unroll
-        for (int v = 0; v < WAVES; ++v) acc += (static_cast<uint32_t>(v) < wave) ? s_tmp[v] : 0u;
+        uint32_t acc = incl - total + waves_before<WAVES>(s_tmp, wave);
         if constexpr (PER == 2) reinterpret_cast<uint2 *>(s_hist)[tid] = make_uint2(acc, acc + c[0]);
         else s_hist[tid] = acc;
     }
@@ -111,16 +143,30 @@ __device__ __forceinline__ void lean_sort_body(uint32_t (&k)[4 * VEC], uint32_t 
         for (int c = 0; c < 4; ++c) {
             uint32_t a = (opaque(k[4 * j + c]) << 2) & 0x7FCu;
             if (ALIGNED_IN ? j >= VEC - 2 : (j == 0 || j == VEC - 1)) {
+                const uint32_t q = 4u * (j * THREADS + tid) + c;
+                a = (q - mis_in < n) ? a : 2048u + 4u * lane;
+            }
+            rank[4 * j + c] += *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_hist) + a);
+        }
+    // The slots without a key read their dummy counter like every other slot and are put right afterwards: written as ONE select over the
+    // read, the compiler makes the select a branch and sinks the read into it -- an LDS round trip per item that nothing overlaps
+    // (tools/isa_audit.py: dep_reads).  pinned(): the sums exist before any select, so every read above is issued back to back.
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+        if (ALIGNED_IN ? j >= VEC - 2 : (j == 0 || j == VEC - 1)) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) pinned(rank[4 * j + c]);
+        }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+        if (ALIGNED_IN ? j >= VEC - 2 : (j == 0 || j == VEC - 1)) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
                 // a slot behind the bucket keeps its place (position q: mis_in + n slots lie before the first of them, mis_in of
                 // those without a key), the ones before the bucket follow the keys (position n + q)
                 const uint32_t q = 4u * (j * THREADS + tid) + c;
-                const bool valid = q - mis_in < n;
-                a = valid ? a : 2048u + 4u * lane;
-                const uint32_t r = rank[4 * j + c] + *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_hist) + a);
-                rank[4 * j + c] = valid ? r : 4u * (q < mis_in ? n + q : q);
-                continue;
+                rank[4 * j + c] = (q - mis_in < n) ? rank[4 * j + c] : 4u * (q < mis_in ? n + q : q);
             }
-            rank[4 * j + c] += *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(s_hist) + a);
         }
     // byte offset Lb = 4 L of position L goes to byte (Lb & ~1023) | ((Lb & 252) << 2) | ((Lb >> 6) & 12)
 #pragma unroll
@@ -176,17 +222,10 @@ __device__ __forceinline__ void lean_sort_body(uint32_t (&k)[4 * VEC], uint32_t 
                 total += c[v][0];
             }
         }
-        uint32_t incl = total;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o);
-            if (lane >= static_cast<uint32_t>(o)) incl += t;
-        }
+        const uint32_t incl = wave_inclusive_sum(total);
         if (lane == 63u) s_tmp[wave] = incl;
         __syncthreads();
-        uint32_t acc = incl - total + 4u * mis;
-#pragma unroll
-        for (int v = 0; v < WAVES; ++v) acc += (static_cast<uint32_t>(v) < wave) ? s_tmp[v] : 0u;
+        uint32_t acc = incl - total + 4u * mis + waves_before<WAVES>(s_tmp, wave);
         uint32_t out[WAVES][PER];
 #pragma unroll
         for (int p_ = 0; p_ < PER; ++p_)
@@ -205,23 +244,28 @@ __device__ __forceinline__ void lean_sort_body(uint32_t (&k)[4 * VEC], uint32_t 
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
         uint32_t a = (opaque(k[i]) >> 7) & 0x7FCu;
-        if (i >= kFirstMaybeEmpty) {  // a slot without a key stays where it is: slot mis + L
-            const uint32_t L = seg + i * 64 + lane;
-            a = L < n ? a : 2048u + 4u * lane;
-            const uint32_t r = rank[i] + *reinterpret_cast<const uint32_t *>(my + a);
-            rank[i] = L < n ? r : 4u * (mis + L);
-            continue;
-        }
+        if (i >= kFirstMaybeEmpty) a = (seg + i * 64 + lane < n) ? a : 2048u + 4u * lane;
         rank[i] += *reinterpret_cast<const uint32_t *>(my + a);
+    }
+    // (reads first, selects afterwards: see pass 1)
+#pragma unroll
+    for (int i = kFirstMaybeEmpty; i < ITEMS; ++i) pinned(rank[i]);
+#pragma unroll
+    for (int i = kFirstMaybeEmpty; i < ITEMS; ++i) {  // a slot without a key stays where it is: slot mis + L
+        const uint32_t L = seg + i * 64 + lane;
+        rank[i] = L < n ? rank[i] : 4u * (mis + L);
     }
     // (every wave read its pass-2 keys out of s_keys before its atomics, and two barriers lie behind those: s_keys is free)
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s_keys) + rank[i]) = k[i];
     __syncthreads();
     // ---- store: slot q = 4 v + c holds sorted position q - mis
+    // (sorted in place, the rows' store addresses are their load addresses: kept alive through both passes they are spilled, and every reload is
+    //  a wait for the stores in front of it -- the thread index made opaque here has them computed again)
+    const uint32_t ts = ALIGNED_IN ? tid : opaque(tid);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-        const uint32_t v = j * THREADS + tid;
+        const uint32_t v = j * THREADS + ts;
         if (j > 0 && j < VEC - 1) {
             store_sorted<STREAM>(reinterpret_cast<uint4 *>(abase) + v, reinterpret_cast<const uint4 *>(s_keys)[v]);
         } else if (v < nvec) {
@@ -248,13 +292,7 @@ __device__ __forceinline__ void wave_phase() {  // orders this wave's LDS traffi
 __device__ __forceinline__ void wave_scan512(uint32_t *tbl, uint32_t lane, uint32_t start) {
     uint4 a = reinterpret_cast<uint4 *>(tbl)[2 * lane], b = reinterpret_cast<uint4 *>(tbl)[2 * lane + 1];
     const uint32_t s = a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w;
-    uint32_t incl = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= static_cast<uint32_t>(o)) incl += t;
-    }
-    uint32_t acc = incl - s + start;
+    uint32_t acc = wave_inclusive_sum(s) - s + start;
     uint4 oa, ob;
     oa.x = acc; acc += a.x; oa.y = acc; acc += a.y; oa.z = acc; acc += a.z; oa.w = acc; acc += a.w;
     ob.x = acc; acc += b.x; ob.y = acc; acc += b.y; ob.z = acc; acc += b.z; ob.w = acc;
@@ -307,14 +345,20 @@ __device__ __forceinline__ void wave_sort_body(uint32_t (&k)[4 * VEC], uint32_t 
         uint32_t a = (opaque(k[i]) << 2) & 0x7FCu;
         if (ALIGNED_IN ? i >= ITEMS - 8 : (i < 4 || i >= ITEMS - 4)) {
             const uint32_t q = 4u * ((i >> 2) * 64 + lane) + (i & 3);
-            const bool valid = q - mis_in < n;
-            a = valid ? a : 2048u + 4u * lane;
-            const uint32_t r = rank[i] + *reinterpret_cast<const uint32_t *>(tb + a);
-            rank[i] = valid ? r : 4u * (q < mis_in ? n + q : q);
-            continue;
+            a = (q - mis_in < n) ? a : 2048u + 4u * lane;
         }
         rank[i] += *reinterpret_cast<const uint32_t *>(tb + a);
     }
+    // (every read issued before any slot without a key is put right: lean_sort_body, pass 1)
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i)
+        if (ALIGNED_IN ? i >= ITEMS - 8 : (i < 4 || i >= ITEMS - 4)) pinned(rank[i]);
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i)
+        if (ALIGNED_IN ? i >= ITEMS - 8 : (i < 4 || i >= ITEMS - 4)) {
+            const uint32_t q = 4u * ((i >> 2) * 64 + lane) + (i & 3);
+            rank[i] = (q - mis_in < n) ? rank[i] : 4u * (q < mis_in ? n + q : q);
+        }
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
         const uint32_t Lb = rank[i];
@@ -344,18 +388,24 @@ __device__ __forceinline__ void wave_sort_body(uint32_t (&k)[4 * VEC], uint32_t 
     wave_phase();
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t L = i * 64 + lane;
         uint32_t a = (opaque(k[i]) >> 7) & 0x7FCu;
-        a = L < n ? a : 2048u + 4u * lane;
-        const uint32_t r = rank[i] + *reinterpret_cast<const uint32_t *>(tb + a);
-        rank[i] = L < n ? r : 4u * (mis + L);
+        a = (i * 64 + lane < n) ? a : 2048u + 4u * lane;
+        rank[i] += *reinterpret_cast<const uint32_t *>(tb + a);
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) pinned(rank[i]);
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t L = i * 64 + lane;
+        rank[i] = L < n ? rank[i] : 4u * (mis + L);
     }
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s_keys) + rank[i]) = k[i];
     wave_phase();
+    const uint32_t ls = ALIGNED_IN ? lane : opaque(lane);  // (see lean_sort_body's stores)
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-        const uint32_t v = j * 64 + lane;
+        const uint32_t v = j * 64 + ls;
         if (v < nvec) {
             const uint4 q4 = reinterpret_cast<const uint4 *>(s_keys)[v];
             const uint32_t q = 4u * v;
@@ -433,12 +483,7 @@ __device__ __forceinline__ void local_pass(K (&key)[ITEMS], uint32_t (&val)[PAIR
                 }
             }
         }
-        uint32_t incl = total;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(incl, o);
-            if (lane >= static_cast<uint32_t>(o)) incl += t;
-        }
+        const uint32_t incl = wave_inclusive_sum(total);  // (lean_sort_body's scans: no LDS round trip per step)
         if (lane == 63u) s_tmp[wave] = incl;
         __syncthreads();
         uint32_t acc = incl - total;

@@ -413,6 +413,7 @@ __device__ __forceinline__ void lean_sort_bucket(uint32_t *abase, uint32_t mis, 
         uint32_t v = j * THREADS + tid;
         if (j == VEC - 1) v = v < nvec ? v : nvec - 1u;  // only the last row can reach behind the bucket
         const uint4 t = reinterpret_cast<const uint4 *>(abase)[v];
+        if (j + 1 < VEC) rows_in_order();  // (vrs_local_sort.hpp: row 0 first -- the skew check below waits for that row alone)
         k[4 * j] = t.x;
         k[4 * j + 1] = t.y;
         k[4 * j + 2] = t.z;
@@ -435,9 +436,12 @@ __device__ __forceinline__ void lean_sort_bucket(uint32_t *abase, uint32_t mis, 
         if (lane == 0u) s_tmp[16 + wave] = skew;
     }
     __syncthreads();
-    uint32_t guards = 0;
+    uint32_t guards = 0;  // (the waves' verdicts in whole 16-byte reads: one LDS round trip, not one per wave)
 #pragma unroll
-    for (int v = 0; v < WAVES; ++v) guards |= s_tmp[16 + v];
+    for (int g = 0; g < WAVES / 4; ++g) {
+        const uint4 t = reinterpret_cast<const uint4 *>(s_tmp + 16)[g];
+        guards |= t.x | t.y | t.z | t.w;
+    }
     guards = __builtin_amdgcn_readfirstlane(guards);
     // Two copies of the rest.  The common one is inlined and carries no trace of the guard; the guarded one is a CALL that loads
     // the bucket again -- kept out of line so that its register demand cannot push the common path into scratch spills (spills
@@ -472,7 +476,7 @@ __global__ __launch_bounds__(THREADS, 4) void msd_local_sort_keys_kernel(uint32_
                                                                          uint32_t *__restrict__ cursors) {
     __shared__ __attribute__((aligned(16))) uint32_t s_keys[THREADS * 4 * kLeanMaxVec + 4];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[(THREADS / 64 + 1) * kLeanRow];
-    __shared__ uint32_t s_tmp[32];
+    __shared__ __attribute__((aligned(16))) uint32_t s_tmp[32];  // (the scans read the waves' totals as 16-byte vectors)
     if (msd->ok == 0u) return;  // enqueued before the plan was known, and the plan refused the hybrid form
     rearm_reservation(cursors, THREADS);
     clear_status_share(sc, THREADS);
@@ -537,7 +541,13 @@ __device__ __forceinline__ void wave_sort_bucket(uint32_t *abase, uint32_t mis, 
     skew = __builtin_amdgcn_readfirstlane(skew);
     wave_phase();
     if (skew == 0u) wave_sort_body<VEC, false>(k, abase, mis, n, s_keys, tbl, false, false, mis);
-    else wave_sort_guarded<VEC>(abase, mis, n, s_keys, tbl, skew);  // out of line, loads the bucket again: see lean_sort_bucket
+    else {  // out of line, loads the bucket again: see lean_sort_bucket
+        // (the copy has this one caller, so the table's LDS address would be propagated into it as a constant -- and the gfx950 backend of ROCm 7's
+        //  clang then fails on wave_sort_body's unconditional counter reads: "Illegal instruction detected".  Handed over as a value it cannot see through.)
+        uint32_t *table = tbl;
+        asm volatile("" : "+v"(table));
+        wave_sort_guarded<VEC>(abase, mis, n, s_keys, table, skew);
+    }
 }
 
 template <int VEC>

@@ -46,9 +46,12 @@ __device__ __forceinline__ void slack_sort_bucket(const uint32_t *src, uint32_t 
         if (lane == 0u) s_tmp[16 + wave] = skew;
     }
     __syncthreads();
-    uint32_t guards = 0;
+    uint32_t guards = 0;  // (the waves' verdicts in whole 16-byte reads: one LDS round trip, not one per wave)
 #pragma unroll
-    for (int v = 0; v < WAVES; ++v) guards |= s_tmp[16 + v];
+    for (int g = 0; g < WAVES / 4; ++g) {
+        const uint4 t = reinterpret_cast<const uint4 *>(s_tmp + 16)[g];
+        guards |= t.x | t.y | t.z | t.w;
+    }
     guards = __builtin_amdgcn_readfirstlane(guards);
     if (guards == 0u) lean_sort_body<THREADS, VEC, false, true, true>(k, abase, mis, n, s_keys, s_hist2, s_tmp, false, false, 0u);
     else slack_sort_guarded<THREADS, VEC>(src, abase, mis, n, s_keys, s_hist2, s_tmp, guards);
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(THREADS, WGS *(THREADS / 64) / 4) void pool_local_s
                                                                                           OnesweepPlanHead *host_head, uint32_t stamp, uint32_t *host_log, uint32_t retry, uint32_t par) {
     __shared__ __attribute__((aligned(16))) uint32_t s_keys[THREADS * 4 * MAXVEC + 4];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[(THREADS / 64 + 1) * kLeanRow];
-    __shared__ uint32_t s_tmp[32];
+    __shared__ __attribute__((aligned(16))) uint32_t s_tmp[32];  // (the scans read the waves' totals as 16-byte vectors)
     const uint32_t *src;
     uint32_t *abase, mis, n;
     if (!pool_bucket<THREADS, THREADS * 4u * MAXVEC, SUBBITS>(slack, keys_out, msd, pool, cursors, dev_head, host_head, stamp, host_log, retry, par, src, abase, mis, n)) return;

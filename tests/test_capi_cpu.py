@@ -10,7 +10,8 @@ import vkradixsort_amd as vrs
 from vkradixsort_amd import capi
 
 ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "vkradixsort_amd.h"
+# the C ABI as it stood before the one header was split by audience: the split may move a name, never add or lose one
+ABI_SYMBOLS = (ROOT / "tests" / "golden" / "c_abi_symbols.txt").read_text().split()
 
 
 @pytest.fixture(scope="module")
@@ -20,17 +21,73 @@ def lib():
     return capi.load_library()
 
 
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"\b(vrs_[a-z0-9_]+)\s*\(", text)))
+def declared_symbols(header):
+    """the functions one header declares, in its order"""
+    text = re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S)
+    return re.findall(r"\b(vrs_[a-z0-9_]+)\s*\(", text)
 
 
 def test_header_symbols_are_all_exported_and_bound(lib):
-    syms = declared_symbols()
-    assert len(syms) >= 25
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in the header but not exported"
-    assert sorted(capi.EXPORTED_SYMBOLS) == syms, "ctypes binding and header diverge"
+    assert [h.name for h in capi.HEADERS] == list(capi._SIGNATURES) and len(capi.HEADERS) == 4
+    assert sorted(h.name for h in (ROOT / "include").iterdir()) == sorted(capi._SIGNATURES)
+    seen = []
+    for header in capi.HEADERS:
+        syms = declared_symbols(header)
+        assert syms == [s[0] for s in capi._SIGNATURES[header.name]], f"ctypes binding and {header.name} diverge"
+        for s in syms:
+            assert hasattr(lib, s), f"{s} declared in {header.name} but not exported"
+            assert s not in seen, f"{s} is declared twice"
+            seen.append(s)
+    assert len(ABI_SYMBOLS) == 146 and sorted(seen) == ABI_SYMBOLS
+    assert capi.EXPORTED_SYMBOLS == seen
+
+
+@pytest.mark.parametrize("language", [("-x", "c", "-std=c11"), ("-x", "c++", "-std=c++17")], ids=["c11", "c++17"])
+def test_every_header_stands_alone(language):
+    """each of the four headers, included first and alone, is strict C11 and strict C++17"""
+    import subprocess
+    for header in capi.HEADERS:
+        p = subprocess.run(["gcc", *language, "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-pedantic", str(header)],
+                           capture_output=True, text=True, timeout=60)
+        assert p.returncode == 0, (header.name, p.stderr)
+
+
+def test_header_constants_equal_the_bindings():
+    """every `VRS_NAME = <integer literal>` enumerator or #define of the headers that capi defines too has the same value there"""
+    compared = 0
+    for header in capi.HEADERS:
+        text = re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S)
+        pairs = re.findall(r"\b(VRS_[A-Z0-9_]+)\s*=\s*(-?\d+)\b", text) + re.findall(r"#define\s+(VRS_[A-Z0-9_]+)\s+(-?\d+)u?\s", text)
+        for name, value in pairs:
+            if hasattr(capi, name):
+                assert getattr(capi, name) == int(value), (header.name, name)
+                compared += 1
+    assert compared >= 130, compared
+    # the two #defines that are expressions, mirrored in capi without the VRS_ prefix
+    dist = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "vkradixsort_amd_dist.h").read_text(), flags=re.S)
+    for name in ("MSD_COUNT_WORDS", "MSD_SHIFT_WORD"):
+        expr = re.search(r"#define\s+VRS_%s\s+\(([0-9u+* ]+)\)" % name, dist).group(1)
+        assert eval(expr.replace("u", "")) == getattr(capi, name), name  # (digits, + and * only: the pattern admits nothing else)
+
+
+def test_the_library_exports_the_declared_abi_and_nothing_else(lib):
+    """built with hidden visibility, every header under a visibility push: the dynamic symbol table holds the 146 declared functions and
+    no helper of the implementation (a mangled vrsh:: or vrs:: name, a global) that another copy of the library could interpose"""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", str(capi.LIB_PATH)], capture_output=True, text=True, check=True, timeout=60).stdout
+    ours = sorted(line.split()[-1] for line in out.splitlines() if line.strip() and "vrs" in line.split()[-1])
+    assert ours == ABI_SYMBOLS, (sorted(set(ours) - set(ABI_SYMBOLS)), sorted(set(ABI_SYMBOLS) - set(ours)))
+
+
+def test_host_mirror_and_single_gpu_examples_include_only_the_core_header():
+    """the C++ host mirror is the drop-in: it needs the boundary header and nothing from the three beside it
+    (test_cpp_host_mirror_builds_and_fails_loudly_without_gpu builds it that way)"""
+    host = ROOT / "vkradixsort_amd" / "host"
+    files = [p for d in ("include", "src") for p in (host / d).rglob("*") if p.is_file()]
+    files += [host / "bin" / "SingleRadixSortExample.cpp", host / "bin" / "MultiRadixSortExample.cpp"]
+    assert len(files) >= 10 and all(p.exists() for p in files)
+    for p in files:
+        assert not re.search(r"vkradixsort_amd_(ops|dist|tune)\.h", p.read_text()), p
 
 
 def test_push_constants_layout_is_16_bytes_std430():
@@ -259,7 +316,7 @@ def test_round3_entry_points_reject_null_and_need_no_device(lib):
 
 
 def test_dist_transport_table_layout():
-    # include/vkradixsort_amd.h: user + seven function pointers, in this order
+    # include/vkradixsort_amd_dist.h: user + seven function pointers, in this order
     assert ctypes.sizeof(capi.DistTransport) == 8 * ctypes.sizeof(ctypes.c_void_p)
     assert [f[0] for f in capi.DistTransport._fields_] == ["user", "all_gather", "all_reduce", "group_start", "send", "recv",
                                                            "group_end", "error_string"]

@@ -149,7 +149,7 @@ def test_tile_key_number_default_and_range(lib):
     assert capi.VRS_TUNE_COMPACT_TILE_ELEMS == 40
     assert (T_DEFAULT, T_MIN, T_MAX) == (16384, 4096, 65536) and T_DEFAULT % 4096 == 0
     assert capi.COMPACT_CHUNK == 4096 and capi.COMPACT_CARRY_BLOCK == 4096 and capi.COMPACT_MAX_DIMS == 8
-    header = (Path(__file__).resolve().parent.parent / "include" / "vkradixsort_amd.h").read_text()
+    header = (Path(__file__).resolve().parent.parent / "include" / "vkradixsort_amd_tune.h").read_text()
     assert "VRS_TUNE_COMPACT_TILE_ELEMS = 40" in header and "Default 16384" in header
     for T in (0, 1, 2048, 4095, 4097, 6144, T_MAX + 4096, 2 ** 31):
         assert _query(lib.vrs_compact_tiles_for, ctypes.c_uint32, 1000, T)[0] == capi.VRS_ERROR_INVALID_ARGUMENT, T

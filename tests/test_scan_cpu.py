@@ -351,10 +351,11 @@ def test_scratch_bytes_over_its_edges(lib, S, L):
 
 
 def test_the_keys_are_37_38_39_in_the_header_and_in_capi():
-    header = (ROOT / "include" / "vkradixsort_amd.h").read_text()
+    header = (ROOT / "include" / "vkradixsort_amd_tune.h").read_text()
     for name, key in (("VRS_TUNE_SCAN_TILE_ROWS", 37), ("VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS", 38), ("VRS_TUNE_SCAN_SPIN_BUDGET", 39)):
         assert re.search(rf"\b{name}\s*=\s*{key}\b", header), name
         assert getattr(capi, name) == key
+    header = (ROOT / "include" / "vkradixsort_amd_ops.h").read_text()
     for name, value in (("VRS_SCAN_SUM", 0), ("VRS_SCAN_PROD", 1), ("VRS_SCAN_MAX", 2), ("VRS_SCAN_MIN", 3), ("VRS_SCAN_TILE", 0),
                         ("VRS_SCAN_THREE_LAUNCH", 1), ("VRS_SCAN_SINGLE_PASS", 2)):
         assert re.search(rf"\b{name}\s*=\s*{value}\b", header) and getattr(capi, name) == value, name

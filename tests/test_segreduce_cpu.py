@@ -77,9 +77,10 @@ def test_new_symbols_are_bound_and_exported():
     assert (capi.VRS_TUNE_REDUCE_CHUNK_ROWS, capi.VRS_TUNE_REDUCE_LANE_ROWS) == (35, 36) and (CH, LR) == (512, 16)
     assert (SUM, PROD, MIN, MAX) == (0, 1, 2, 3) and (LANE, ROWS, COLUMNS) == (0, 1, 2)
     from pathlib import Path
-    header = (Path(__file__).resolve().parent.parent / "include" / "vkradixsort_amd.h").read_text()
+    include = Path(__file__).resolve().parent.parent / "include"
+    header = (include / "vkradixsort_amd_tune.h").read_text()
     assert re.search(r"VRS_TUNE_REDUCE_CHUNK_ROWS\s*=\s*35\b", header) and re.search(r"VRS_TUNE_REDUCE_LANE_ROWS\s*=\s*36\b", header)
-    assert "K13" in header
+    assert "K13" in (include / "vkradixsort_amd_ops.h").read_text()
 
 
 def map_for(lib, rows, C, lr=LR):

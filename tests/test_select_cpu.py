@@ -25,7 +25,7 @@ def rank_bytes(dtype):
 
 
 def test_new_symbols_are_bound_and_exported(lib):
-    header = (Path(__file__).resolve().parents[1] / "include" / "vkradixsort_amd.h").read_text()
+    header = "".join(h.read_text() for h in capi.HEADERS)
     for name in NEW_SYMBOLS:
         assert name in capi.EXPORTED_SYMBOLS
         assert re.search(r"\b%s\s*\(" % name, header), name
@@ -36,7 +36,7 @@ def test_new_symbols_are_bound_and_exported(lib):
 def test_tune_keys_and_defaults():
     assert (capi.VRS_TUNE_SELECT_GRID_MIN_KEYS, capi.VRS_TUNE_SELECT_COMPACT_DIVISOR) == (33, 34)
     assert (capi.SELECT_GRID_MIN_KEYS_DEFAULT, capi.SELECT_COMPACT_DIVISOR_DEFAULT) == (1 << 17, 16)
-    header = (Path(__file__).resolve().parents[1] / "include" / "vkradixsort_amd.h").read_text()
+    header = (Path(__file__).resolve().parents[1] / "include" / "vkradixsort_amd_tune.h").read_text()
     assert re.search(r"VRS_TUNE_SELECT_GRID_MIN_KEYS\s*=\s*33\b", header)
     assert re.search(r"VRS_TUNE_SELECT_COMPACT_DIVISOR\s*=\s*34\b", header)
     assert re.search(r"VRS_KERNEL_COUNT\s*=\s*10\b", header) and capi.VRS_KERNEL_COUNT == 10

@@ -15,7 +15,8 @@ if os.environ.get("VRS_LIB"):
 if os.environ.get("VRS_LIB_LENIENT"):  # timing an older build of the library: drop the entry points it does not have yet
     import ctypes
     _probe = ctypes.CDLL(str(capi.LIB_PATH))
-    capi._SIGNATURES[:] = [sig for sig in capi._SIGNATURES if hasattr(_probe, sig[0])]
+    for _sigs in capi._SIGNATURES.values():
+        _sigs[:] = [sig for sig in _sigs if hasattr(_probe, sig[0])]
 import vkradixsort_amd as vrs  # noqa: E402
 
 tag = sys.argv[1]

@@ -1,6 +1,6 @@
 """vkradixsort_amd -- MI355X-native multi-block LSD radix sort behind VkRadixSort's MultiRadixSort host API.
 
-csrc/    hand-written gfx950 HIP kernels + the C ABI (include/vkradixsort_amd.h)
+csrc/    hand-written gfx950 HIP kernels + the C ABI (include/vkradixsort_amd*.h)
 host/    C++ mirror of the reference's host classes (engine::GPUContext, Buffer, MultiRadixSortPass, ...)
 engine   the same interface for Python callers (tests, bench.py), a thin ctypes layer over the C ABI
 segmented  many independent segments sorted in one call (sort_segments over Buffers, sort_rows for 2-D torch tensors)

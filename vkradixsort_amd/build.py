@@ -26,8 +26,10 @@ HIP_SOURCES = [CSRC / name for name in ("vrs_contract.hip", "vrs_one_call.hip", 
                                         "vrs_segreduce.hip", "vrs_capi_segreduce.hip",
                                         "vrs_scan.hip", "vrs_scan_pairs.hip", "vrs_capi_scan.hip",
                                         "vrs_compact.hip", "vrs_capi_compact.hip")]
-HIP_HEADERS = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + [INCLUDE / "vkradixsort_amd.h"]  # every object is rebuilt when any header is newer
+PUBLIC_HEADERS = sorted(INCLUDE.glob("*.h"))  # the C ABI, one header per audience
+HIP_HEADERS = sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + PUBLIC_HEADERS  # every object is rebuilt when any header is newer
 ARCH = "gfx950"
+EXPORT_MAP = CSRC / "libvkradixsort_amd.map"  # the library exports the declared C ABI (vrs_*) and nothing else
 
 
 def _hipcc() -> str:
@@ -59,10 +61,10 @@ def build_library(force: bool = False) -> Path:
     objs = [obj_dir / (src.stem + ".o") for src in HIP_SOURCES]
     stale = [(src, obj) for src, obj in zip(HIP_SOURCES, objs) if force or _stale(obj, [src] + HIP_HEADERS)]
     with ThreadPoolExecutor(max_workers=max(len(stale), 1)) as pool:
-        list(pool.map(lambda so: _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c",
+        list(pool.map(lambda so: _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-c",
                                        f"-I{INCLUDE}", f"-I{CSRC}", so[0], "-o", so[1]]), stale))
-    if stale or force or _stale(LIB_PATH, objs):
-        _run([_hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", *objs, "-ldl", "-o", LIB_PATH])
+    if stale or force or _stale(LIB_PATH, objs + [EXPORT_MAP]):
+        _run([_hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", f"-Wl,--version-script={EXPORT_MAP}", *objs, "-ldl", "-o", LIB_PATH])
     return LIB_PATH
 
 
@@ -75,7 +77,7 @@ def build_host(force: bool = False):
     libvkradixsort_host.so plus the two example executables.  Links only the C ABI."""
     build_library(force)
     out_lib = PKG_DIR / "libvkradixsort_host.so"
-    hdrs = list((HOST / "include").rglob("*.h")) + [INCLUDE / "vkradixsort_amd.h"]
+    hdrs = list((HOST / "include").rglob("*.h")) + PUBLIC_HEADERS
     srcs = host_sources()
     cxx = shutil.which("g++") or "g++"
     common = ["-O2", "-std=c++20", "-fPIC", f"-I{HOST / 'include'}", f"-I{INCLUDE}"]
@@ -98,7 +100,7 @@ def build_dist_example(force: bool = False) -> Path:
     build_library(force)
     src = HOST / "bin" / "DistSortExample.cpp"
     exe = PKG_DIR / "distsortexample"
-    if force or _stale(exe, [src, LIB_PATH, INCLUDE / "vkradixsort_amd.h"]):
+    if force or _stale(exe, [src, LIB_PATH, *PUBLIC_HEADERS]):
         cxx = shutil.which("g++") or "g++"
         _run([cxx, "-O2", "-std=c++20", "-pthread", f"-I{INCLUDE}", src, "-o", exe, f"-L{PKG_DIR}", "-lvkradixsort_amd",
               "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"])
@@ -110,7 +112,7 @@ def build_host_logic_test(force: bool = False) -> Path:
     out_lib, _ = build_host(force)
     src = HOST / "test" / "host_logic_test.cpp"
     exe = PKG_DIR / "host_logic_test"
-    hdrs = list((HOST / "include").rglob("*.h")) + [INCLUDE / "vkradixsort_amd.h"]
+    hdrs = list((HOST / "include").rglob("*.h")) + PUBLIC_HEADERS
     if force or _stale(exe, [src, out_lib] + hdrs):
         cxx = shutil.which("g++") or "g++"
         _run([cxx, "-O2", "-std=c++20", f"-I{HOST / 'include'}", f"-I{INCLUDE}", src, "-o", exe, f"-L{PKG_DIR}",
@@ -154,16 +156,17 @@ def build_sanitized(kind: str = "asan", force: bool = False) -> dict:
     objs = [out / (src.stem + ".o") for src in HIP_SOURCES]
     stale = [(src, obj) for src, obj in zip(HIP_SOURCES, objs) if force or _stale(obj, [src] + HIP_HEADERS)]
     with ThreadPoolExecutor(max_workers=max(len(stale), 1)) as pool:
-        list(pool.map(lambda so: _run([_hipcc(), f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-fno-gpu-sanitize", "-shared-libsan", *flags, "-c",
+        list(pool.map(lambda so: _run([_hipcc(), f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-gpu-sanitize", "-shared-libsan", *flags, "-c",
                                        f"-I{INCLUDE}", f"-I{CSRC}", so[0], "-o", so[1]]), stale))
-    if stale or force or _stale(lib, objs):
-        _run([_hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", "-fno-gpu-sanitize", "-shared-libsan", *flags, *objs, "-ldl", "-o", lib])
+    if stale or force or _stale(lib, objs + [EXPORT_MAP]):
+        _run([_hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", f"-Wl,--version-script={EXPORT_MAP}", "-fno-gpu-sanitize", "-shared-libsan", *flags, *objs,
+              "-ldl", "-o", lib])
     cxx = _clangxx()
     rt_dir = subprocess.run([cxx, "-print-runtime-dir"], capture_output=True, text=True).stdout.strip()
     rt_alt = str(Path(rt_dir).parent / "linux")  # (where ROCm's clang keeps libclang_rt.*-x86_64.so)
     common = ["-std=c++20", "-fPIC", "-pthread", "-shared-libsan", *flags, f"-I{HOST / 'include'}", f"-I{INCLUDE}"]
     link = [f"-L{out}", "-lvkradixsort_amd", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib", f"-Wl,-rpath,{rt_dir}", f"-Wl,-rpath,{rt_alt}"]
-    hdrs = list((HOST / "include").rglob("*.h")) + [INCLUDE / "vkradixsort_amd.h"]
+    hdrs = list((HOST / "include").rglob("*.h")) + PUBLIC_HEADERS
     exes = {}
     # (the host mirror's sources go INTO the test executable: as a second instrumented shared library its globals were registered twice by
     #  the runtime -- reported as a violation of the one-definition rule although nothing is defined twice)

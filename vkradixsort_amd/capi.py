@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/vkradixsort_amd.h (the ONLY way Python reaches the GPU path).
+"""ctypes binding of the C ABI in the four headers under include/ (HEADERS below; the ONLY way Python reaches the GPU path).
 
 There is no fallback: if libvkradixsort_amd.so has not been built, or no HIP device is present, the
 calls raise.  Nothing here imports or knows about oracle/.
@@ -165,13 +165,13 @@ class VrsError(RuntimeError):
 
 
 class DistTransport(ctypes.Structure):
-    """vrs_dist_transport: the wire of the multi-GPU step as a table of functions (include/vkradixsort_amd.h)."""
+    """vrs_dist_transport: the wire of the multi-GPU step as a table of functions (include/vkradixsort_amd_dist.h)."""
     _fields_ = [("user", c_void_p), ("all_gather", c_void_p), ("all_reduce", c_void_p), ("group_start", c_void_p),
                 ("send", c_void_p), ("recv", c_void_p), ("group_end", c_void_p), ("error_string", c_void_p)]
 
 
 class CompactOutputs(ctypes.Structure):
-    """vrs_compact_outputs: what vrs_compact_emit writes (include/vkradixsort_amd.h "K15")."""
+    """vrs_compact_outputs: what vrs_compact_emit writes (include/vkradixsort_amd_ops.h "K15")."""
     _fields_ = [("num_selected", c_uint64), ("flat", c_void_p), ("coords", c_void_p), ("coords_layout", c_int), ("ndim", c_uint32),
                 ("shape", c_uint32 * 8), ("gather_values", c_void_p), ("gather_out", c_void_p), ("value_bytes", c_uint32),
                 ("reserved", c_uint32), ("scatter_input", c_void_p), ("scatter_source", c_void_p), ("scatter_out", c_void_p)]
@@ -187,161 +187,171 @@ class CompactHostOutputs(ctypes.Structure):
 MSD_COUNT_WORDS = 16384 + 8 * 256 + 64
 MSD_SHIFT_WORD = 16384 + 8 * 256
 
-# every symbol include/vkradixsort_amd.h declares: (name, restype, argtypes)
-_SIGNATURES = [
-    ("vrs_version", c_char_p, []),
-    ("vrs_device_count", c_int, [POINTER(c_int)]),
-    ("vrs_context_create", c_int, [c_int, POINTER(c_void_p)]),
-    ("vrs_context_create_on_stream", c_int, [c_int, c_void_p, POINTER(c_void_p)]),
-    ("vrs_context_destroy", c_int, [c_void_p]),
-    ("vrs_last_error", c_char_p, [c_void_p]),
-    ("vrs_context_stream", c_void_p, [c_void_p]),
-    ("vrs_device_info", c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_int), POINTER(c_uint64)]),
-    ("vrs_buffer_create", c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
-    ("vrs_buffer_wrap", c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p)]),
-    ("vrs_buffer_release", c_int, [c_void_p]),
-    ("vrs_buffer_upload", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
-    ("vrs_buffer_download", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
-    ("vrs_buffer_copy", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
-    ("vrs_buffer_device_ptr", c_void_p, [c_void_p]),
-    ("vrs_buffer_size_bytes", c_size_t, [c_void_p]),
-    ("vrs_global_invocation_size", c_uint32, [c_uint32, c_uint32]),
-    ("vrs_workgroup_count", c_uint32, [c_uint32, c_uint32]),
-    ("vrs_multi_radixsort_histograms", c_int, [c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
-    ("vrs_multi_radixsort", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
-    ("vrs_multi_radixsort_pairs", c_int,
-     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
-    ("vrs_multi_radixsort_histograms_u64", c_int, [c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
-    ("vrs_multi_radixsort_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
-    ("vrs_multi_radixsort_pairs_u64", c_int,
-     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
-    ("vrs_range_partition", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]),
-    ("vrs_multi_radixsort_digit_offsets", c_int, [c_void_p, c_void_p]),
-    ("vrs_multi_radixsort_digit_offsets_device", c_int, [c_void_p, c_void_p]),
-    ("vrs_queue_wait_idle", c_int, [c_void_p]),
-    ("vrs_single_radixsort", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("vrs_sort_keys_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("vrs_sort_keys_u32_ranged", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]),
-    ("vrs_sort_settle", c_int, [c_void_p]),
-    ("vrs_sort_pending", c_int, [c_void_p]),
-    ("vrs_sort_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("vrs_sort_pairs_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("vrs_sort_keys_u64", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("vrs_transform_keys", c_int, [c_void_p, c_void_p, c_uint32, c_int]),
-    ("vrs_profile_enable", c_int, [c_void_p, c_int]),
-    ("vrs_profile_enable_mask", c_int, [c_void_p, c_uint32]),
-    ("vrs_verify_keys_u32", c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_dist_create", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_int, POINTER(c_void_p)]),
-    ("vrs_dist_create_with_transport", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_int, POINTER(c_void_p)]),
-    ("vrs_dist_destroy", c_int, [c_void_p]),
-    ("vrs_dist_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_dist_plan_sampled_splitters", c_int, [POINTER(c_uint32), POINTER(c_uint64), c_int, c_uint32, c_int, POINTER(c_uint32)]),
-    ("vrs_dist_grouped_rounds", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_dist_splitter_steps", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_dist_loopback_create", c_int, [c_int, POINTER(c_void_p)]),
-    ("vrs_dist_loopback_create_host", c_int, [c_int, POINTER(c_void_p)]),
-    ("vrs_dist_loopback_set_wire", c_int, [c_void_p, c_double, c_double]),
-    ("vrs_dist_loopback_transport", c_int, [c_void_p, c_int, c_void_p]),
-    ("vrs_dist_loopback_destroy", c_int, [c_void_p]),
-    ("vrs_msd_partition_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("vrs_msd_finish_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]),
-    ("vrs_multi_radixsort_offsets_hook", c_int, [c_void_p, c_void_p, c_void_p]),
-    ("vrs_msd_partition_signal_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
-    ("vrs_msd_finish_grouped_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32]),
-    ("vrs_msd_finish_grouped_counts_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_uint32)]),
-    ("vrs_msd_finish_grouped_split_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
-    ("vrs_msd_finish_status", c_int, [c_void_p, POINTER(c_int)]),
-    ("vrs_msd_finish_ticket", c_int, [c_void_p, POINTER(c_uint32)]),
-    ("vrs_msd_finish_status_at", c_int, [c_void_p, c_uint32, POINTER(c_int)]),
-    ("vrs_context_device", c_int, [c_void_p]),
-    ("vrs_dist_sort_keys_u32", c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_uint32)]),
-    ("vrs_dist_plan_splitters", c_int, [POINTER(c_uint64), c_int, POINTER(c_uint32)]),
-    ("vrs_dist_last_error", c_char_p, [c_void_p]),
-    ("vrs_profile_reset", c_int, [c_void_p]),
-    ("vrs_profile_query", c_int, [c_void_p, c_int, POINTER(c_uint64), POINTER(c_double)]),
-    ("vrs_profile_query_launch", c_int, [c_void_p, c_int, c_uint64, POINTER(c_double)]),
-    ("vrs_one_call_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_one_call_relaunched_passes", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_one_call_hybrid_sorts", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_one_call_hybrid_recounts", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_one_call_pool_sorts", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_one_call_pool_retries", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_one_call_pool_layouts", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_pool_form_shape", c_int, [c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint64)]),
-    ("vrs_sort_form_for", c_int, [c_uint32, c_int, c_int, POINTER(ctypes.c_int64), c_int, POINTER(c_int), POINTER(ctypes.c_int64)]),
-    ("vrs_pool_form_shape_ex", c_int, [c_uint32, c_int, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint64)]),
-    ("vrs_context_trim_scratch", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_one_call_pool_no_memory", c_int, [c_void_p, POINTER(c_uint64)]),
-    ("vrs_debug_xcc_placement", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int)]),
-    ("vrs_debug_download_offsets", c_int, [c_void_p, c_void_p, c_size_t]),
-    ("vrs_debug_atomic_rank_selftest", c_int, [c_void_p, c_uint32, c_uint32, POINTER(c_uint64)]),
-    ("vrs_rank_mode", c_int, [c_void_p]),
-    ("vrs_set_tuning", c_int, [c_void_p, c_int, c_int]),
-    ("vrs_sort_segments_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
-    ("vrs_sort_segments_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
-    ("vrs_segmented_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_segment_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
-    ("vrs_sort_segments_u64", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
-    ("vrs_sort_segments_pairs_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
-    ("vrs_segment_tier_for_u64", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
-    ("vrs_sort_rank_keys", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p]),
-    ("vrs_sort_restore", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p]),
-    ("vrs_sort_rank_bytes", c_int, [c_int, POINTER(c_int)]),
-    ("vrs_topk_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
-    ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
-    ("vrs_topk_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_select_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, c_int, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
-    ("vrs_select_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
-    ("vrs_select_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
-    ("vrs_select_target_for", c_int, [c_int, c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_int)]),
-    ("vrs_select_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_quantile_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, POINTER(c_double), c_uint32, c_int, c_int, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p]),
-    ("vrs_quantile_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
-    ("vrs_quantile_target_for", c_int, [c_int, c_int, c_double, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_double), POINTER(c_int)]),
-    ("vrs_quantile_level_for", c_int, [c_int, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
-    ("vrs_quantile_host", c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_int, POINTER(c_double), c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    ("vrs_quantile_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_search_sorted", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    ("vrs_search_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
-    ("vrs_search_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, c_int, c_int, POINTER(c_uint64)]),
-    ("vrs_search_plan", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
-    ("vrs_search_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_bin_count", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_int, c_double, c_double, c_uint32, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                              c_void_p]),
-    ("vrs_bin_count_tier_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
-    ("vrs_bin_count_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
-    ("vrs_bin_count_plan", c_int, [c_void_p, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
-    ("vrs_bin_count_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_bin_linear_host", c_int, [c_void_p, c_uint64, c_int, c_double, c_double, c_uint32, c_void_p]),
-    ("vrs_segment_reduce", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
-    ("vrs_segment_reduce_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint64)]),
-    ("vrs_segment_reduce_map_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
-    ("vrs_segment_reduce_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
-    ("vrs_segment_reduce_host", c_int, [c_void_p, c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_uint32, c_uint32, c_void_p]),
-    ("vrs_segment_reduce_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_scan_rows", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    ("vrs_scan_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_int)]),
-    ("vrs_scan_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
-    ("vrs_scan_depth_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_uint32)]),
-    ("vrs_scan_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_uint64)]),
-    ("vrs_scan_rows_host", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p]),
-    ("vrs_scan_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_compact_count", c_int, [c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_void_p, POINTER(c_uint64)]),
-    ("vrs_compact_emit", c_int, [c_void_p, c_void_p, c_uint64, c_int, c_void_p, POINTER(CompactOutputs)]),
-    ("vrs_compact_tiles_for", c_int, [c_uint64, c_uint32, POINTER(c_uint32)]),
-    ("vrs_compact_scratch_bytes", c_int, [c_uint64, c_uint32, POINTER(c_uint64)]),
-    ("vrs_compact_divide", c_int, [c_uint32, c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
-    ("vrs_compact_host", c_int, [c_void_p, c_uint64, c_int, POINTER(CompactHostOutputs), POINTER(c_uint64)]),
-    ("vrs_compact_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
-    ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
-    ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    ("vrs_unique_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
-]
+HEADERS = [Path(__file__).resolve().parent.parent / "include" / name for name in ("vkradixsort_amd.h", "vkradixsort_amd_ops.h", "vkradixsort_amd_dist.h", "vkradixsort_amd_tune.h")]
 
-EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
+# every symbol the four headers declare, per header and in the header's order: (name, restype, argtypes)
+_SIGNATURES = {
+    "vkradixsort_amd.h": [
+        ("vrs_device_count", c_int, [POINTER(c_int)]),
+        ("vrs_context_create", c_int, [c_int, POINTER(c_void_p)]),
+        ("vrs_context_create_on_stream", c_int, [c_int, c_void_p, POINTER(c_void_p)]),
+        ("vrs_context_destroy", c_int, [c_void_p]),
+        ("vrs_last_error", c_char_p, [c_void_p]),
+        ("vrs_context_stream", c_void_p, [c_void_p]),
+        ("vrs_context_device", c_int, [c_void_p]),
+        ("vrs_device_info", c_int, [c_void_p, c_char_p, c_size_t, POINTER(c_int), POINTER(c_uint64)]),
+        ("vrs_context_trim_scratch", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_buffer_create", c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
+        ("vrs_buffer_wrap", c_int, [c_void_p, c_void_p, c_size_t, POINTER(c_void_p)]),
+        ("vrs_buffer_release", c_int, [c_void_p]),
+        ("vrs_buffer_upload", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+        ("vrs_buffer_download", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+        ("vrs_buffer_copy", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+        ("vrs_buffer_device_ptr", c_void_p, [c_void_p]),
+        ("vrs_buffer_size_bytes", c_size_t, [c_void_p]),
+        ("vrs_global_invocation_size", c_uint32, [c_uint32, c_uint32]),
+        ("vrs_workgroup_count", c_uint32, [c_uint32, c_uint32]),
+        ("vrs_multi_radixsort_histograms", c_int, [c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
+        ("vrs_multi_radixsort", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
+        ("vrs_multi_radixsort_pairs", c_int,
+         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
+        ("vrs_multi_radixsort_digit_offsets", c_int, [c_void_p, c_void_p]),
+        ("vrs_multi_radixsort_histograms_u64", c_int, [c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
+        ("vrs_multi_radixsort_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
+        ("vrs_multi_radixsort_pairs_u64", c_int,
+         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(PushConstants)]),
+        ("vrs_queue_wait_idle", c_int, [c_void_p]),
+        ("vrs_single_radixsort", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
+        ("vrs_sort_keys_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
+        ("vrs_sort_settle", c_int, [c_void_p]),
+        ("vrs_sort_pending", c_int, [c_void_p]),
+        ("vrs_sort_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+        ("vrs_sort_keys_u64", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
+        ("vrs_sort_pairs_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+        ("vrs_transform_keys", c_int, [c_void_p, c_void_p, c_uint32, c_int]),
+        ("vrs_verify_keys_u32", c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_version", c_char_p, []),
+    ],
+    "vkradixsort_amd_ops.h": [
+        ("vrs_sort_segments_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+        ("vrs_sort_segments_pairs_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+        ("vrs_segmented_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_segment_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+        ("vrs_sort_segments_u64", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+        ("vrs_sort_segments_pairs_u64", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]),
+        ("vrs_segment_tier_for_u64", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+        ("vrs_sort_rank_keys", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p]),
+        ("vrs_sort_restore", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p]),
+        ("vrs_sort_rank_bytes", c_int, [c_int, POINTER(c_int)]),
+        ("vrs_topk_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+        ("vrs_topk_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+        ("vrs_topk_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_int), POINTER(c_uint32), POINTER(c_uint32)]),
+        ("vrs_topk_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_select_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, c_int, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
+        ("vrs_select_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+        ("vrs_select_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
+        ("vrs_select_target_for", c_int, [c_int, c_uint32, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_int)]),
+        ("vrs_select_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_quantile_segments", c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, POINTER(c_double), c_uint32, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+        ("vrs_quantile_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, POINTER(c_uint64)]),
+        ("vrs_quantile_target_for", c_int, [c_int, c_int, c_double, c_uint32, c_uint32, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_double), POINTER(c_int)]),
+        ("vrs_quantile_level_for", c_int, [c_int, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
+        ("vrs_quantile_host", c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_int, POINTER(c_double), c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+        ("vrs_quantile_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_search_sorted", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+        ("vrs_search_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
+        ("vrs_search_scratch_bytes", c_int, [c_uint32, c_uint32, c_int, c_int, c_int, POINTER(c_uint64)]),
+        ("vrs_search_plan", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
+        ("vrs_search_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_bin_count", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_int, c_double, c_double, c_uint32, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
+        ("vrs_bin_count_tier_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
+        ("vrs_bin_count_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
+        ("vrs_bin_count_plan", c_int, [c_void_p, c_uint32, c_int, c_int, POINTER(c_int), POINTER(c_uint64)]),
+        ("vrs_bin_count_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_bin_linear_host", c_int, [c_void_p, c_uint64, c_int, c_double, c_double, c_uint32, c_void_p]),
+        ("vrs_segment_reduce", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p]),
+        ("vrs_segment_reduce_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_uint32, POINTER(c_uint64)]),
+        ("vrs_segment_reduce_map_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_int)]),
+        ("vrs_segment_reduce_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
+        ("vrs_segment_reduce_host", c_int, [c_void_p, c_uint64, c_uint32, c_int, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_uint32, c_uint32, c_void_p]),
+        ("vrs_segment_reduce_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_scan_rows", c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+        ("vrs_scan_tier_for", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_int)]),
+        ("vrs_scan_levels_for", c_int, [c_uint32, c_uint32, POINTER(c_uint32)]),
+        ("vrs_scan_depth_for", c_int, [c_uint32, c_uint32, c_uint32, POINTER(c_uint32)]),
+        ("vrs_scan_scratch_bytes", c_int, [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_uint32, POINTER(c_uint64)]),
+        ("vrs_scan_rows_host", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_uint32, c_void_p, c_void_p]),
+        ("vrs_scan_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_compact_count", c_int, [c_void_p, c_void_p, c_uint64, c_int, c_void_p, c_void_p, POINTER(c_uint64)]),
+        ("vrs_compact_emit", c_int, [c_void_p, c_void_p, c_uint64, c_int, c_void_p, POINTER(CompactOutputs)]),
+        ("vrs_compact_tiles_for", c_int, [c_uint64, c_uint32, POINTER(c_uint32)]),
+        ("vrs_compact_scratch_bytes", c_int, [c_uint64, c_uint32, POINTER(c_uint64)]),
+        ("vrs_compact_divide", c_int, [c_uint32, c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
+        ("vrs_compact_host", c_int, [c_void_p, c_uint64, c_int, POINTER(CompactHostOutputs), POINTER(c_uint64)]),
+        ("vrs_compact_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_run_length_encode", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        ("vrs_run_length_encode_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
+        ("vrs_unique", c_int, [c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        ("vrs_unique_scratch_bytes", c_int, [c_uint32, c_int, c_int, POINTER(c_uint64)]),
+    ],
+    "vkradixsort_amd_dist.h": [
+        ("vrs_sort_keys_u32_ranged", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]),
+        ("vrs_range_partition", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]),
+        ("vrs_multi_radixsort_digit_offsets_device", c_int, [c_void_p, c_void_p]),
+        ("vrs_multi_radixsort_offsets_hook", c_int, [c_void_p, c_void_p, c_void_p]),
+        ("vrs_msd_partition_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+        ("vrs_msd_partition_signal_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+        ("vrs_msd_finish_u32", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]),
+        ("vrs_msd_finish_grouped_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32]),
+        ("vrs_msd_finish_grouped_counts_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_uint32)]),
+        ("vrs_msd_finish_grouped_split_u32", c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_uint32), POINTER(c_uint32)]),
+        ("vrs_msd_finish_status", c_int, [c_void_p, POINTER(c_int)]),
+        ("vrs_msd_finish_ticket", c_int, [c_void_p, POINTER(c_uint32)]),
+        ("vrs_msd_finish_status_at", c_int, [c_void_p, c_uint32, POINTER(c_int)]),
+        ("vrs_dist_create", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_int, POINTER(c_void_p)]),
+        ("vrs_dist_create_with_transport", c_int, [c_void_p, c_void_p, c_int, c_int, c_uint32, c_int, POINTER(c_void_p)]),
+        ("vrs_dist_destroy", c_int, [c_void_p]),
+        ("vrs_dist_sort_keys_u32", c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_uint32)]),
+        ("vrs_dist_plan_splitters", c_int, [POINTER(c_uint64), c_int, POINTER(c_uint32)]),
+        ("vrs_dist_plan_sampled_splitters", c_int, [POINTER(c_uint32), POINTER(c_uint64), c_int, c_uint32, c_int, POINTER(c_uint32)]),
+        ("vrs_dist_last_error", c_char_p, [c_void_p]),
+        ("vrs_dist_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_dist_grouped_rounds", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_dist_splitter_steps", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_dist_loopback_create", c_int, [c_int, POINTER(c_void_p)]),
+        ("vrs_dist_loopback_create_host", c_int, [c_int, POINTER(c_void_p)]),
+        ("vrs_dist_loopback_transport", c_int, [c_void_p, c_int, c_void_p]),
+        ("vrs_dist_loopback_destroy", c_int, [c_void_p]),
+        ("vrs_dist_loopback_set_wire", c_int, [c_void_p, c_double, c_double]),
+    ],
+    "vkradixsort_amd_tune.h": [
+        ("vrs_profile_enable", c_int, [c_void_p, c_int]),
+        ("vrs_profile_enable_mask", c_int, [c_void_p, c_uint32]),
+        ("vrs_profile_reset", c_int, [c_void_p]),
+        ("vrs_profile_query", c_int, [c_void_p, c_int, POINTER(c_uint64), POINTER(c_double)]),
+        ("vrs_profile_query_launch", c_int, [c_void_p, c_int, c_uint64, POINTER(c_double)]),
+        ("vrs_one_call_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_one_call_relaunched_passes", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_one_call_hybrid_sorts", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_one_call_hybrid_recounts", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_sort_form_for", c_int, [c_uint32, c_int, c_int, POINTER(ctypes.c_int64), c_int, POINTER(c_int), POINTER(ctypes.c_int64)]),
+        ("vrs_one_call_pool_sorts", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_pool_form_shape", c_int, [c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint64)]),
+        ("vrs_pool_form_shape_ex", c_int, [c_uint32, c_int, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint64)]),
+        ("vrs_one_call_pool_retries", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_one_call_pool_no_memory", c_int, [c_void_p, POINTER(c_uint64)]),
+        ("vrs_one_call_pool_layouts", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+        ("vrs_rank_mode", c_int, [c_void_p]),
+        ("vrs_set_tuning", c_int, [c_void_p, c_int, c_int]),
+        ("vrs_debug_download_offsets", c_int, [c_void_p, c_void_p, c_size_t]),
+        ("vrs_debug_atomic_rank_selftest", c_int, [c_void_p, c_uint32, c_uint32, POINTER(c_uint64)]),
+        ("vrs_debug_xcc_placement", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int)]),
+    ],
+}
+
+EXPORTED_SYMBOLS = [s[0] for sigs in _SIGNATURES.values() for s in sigs]
 
 _lib = None
 
@@ -378,8 +388,8 @@ def load_library() -> ctypes.CDLL:
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). There is no CPU fallback.")
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, restype, argtypes in _SIGNATURES:
-        fn = getattr(lib, name)  # AttributeError if the header and the library ever diverge
+    for name, restype, argtypes in (sig for sigs in _SIGNATURES.values() for sig in sigs):
+        fn = getattr(lib, name)  # AttributeError if the headers and the library ever diverge
         fn.restype = restype
         fn.argtypes = argtypes
     _lib = lib

@@ -1,4 +1,4 @@
-// vrs_capi.hip -- the C ABI declared in include/vkradixsort_amd.h, part 1 of 5: contexts, buffers, the helpers every part shares
+// vrs_capi.hip -- the C ABI declared in include/vkradixsort_amd*.h, part 1 of 5: contexts, buffers, the helpers every part shares
 // (errors, scratch, profiling events, the placement probe), measurement, tuning and diagnostics.  Host side only.
 // There is NO CPU fallback: without a HIP device every entry point fails with VRS_ERROR_NO_DEVICE.
 // The other parts: vrs_capi_contract.hip (the reference's two stages, single_radixsort, range partition), vrs_capi_sort.hip (the one-call

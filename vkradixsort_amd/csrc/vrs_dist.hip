@@ -53,6 +53,7 @@
 #include <vector>
 
 #include "vkradixsort_amd.h"
+#include "vkradixsort_amd_dist.h"
 
 namespace {
 

@@ -2,6 +2,9 @@
 // and the prototypes of the host functions that cross a file boundary.  Internal: never installed, never included by a caller.
 #pragma once
 #include "vkradixsort_amd.h"
+#include "vkradixsort_amd_dist.h"
+#include "vkradixsort_amd_ops.h"
+#include "vkradixsort_amd_tune.h"
 
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 // vrs_kernels.h -- launch wrappers of the gfx950 kernels (internal; the public surface is
-// include/vkradixsort_amd.h).
+// include/vkradixsort_amd*.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>

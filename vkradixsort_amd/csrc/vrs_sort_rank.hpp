@@ -7,7 +7,7 @@
 
 namespace vrs {
 
-// vrs_sort_dtype (include/vkradixsort_amd.h)
+// vrs_sort_dtype (include/vkradixsort_amd_ops.h)
 constexpr int kSortI8 = 0, kSortU8 = 1, kSortI16 = 2, kSortI32 = 3, kSortI64 = 4, kSortF16 = 5, kSortBF16 = 6, kSortF32 = 7, kSortF64 = 8;
 constexpr int kSortDescending = 1;  // VRS_SORT_DESCENDING
 

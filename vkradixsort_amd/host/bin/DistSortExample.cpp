@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "vkradixsort_amd.h"
+#include "vkradixsort_amd_dist.h"
 
 namespace {
 void check(int rc, vrs_context ctx, const char *what) {

@@ -4,6 +4,8 @@
 // defined (engine/include/engine/core/GPUContext.h:84-90): a debug build that checks the host's use of the API.
 //   arguments: [hub] = only the loopback hub's rendezvous (the part worth running under TSan)
 #include "vkradixsort_amd.h"
+#include "vkradixsort_amd_dist.h"
+#include "vkradixsort_amd_tune.h"
 
 #include <algorithm>
 #include <atomic>

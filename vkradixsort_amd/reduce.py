@@ -1,6 +1,6 @@
 """torch.segment_reduce, index_add, index_reduce and scatter_reduce drop-ins with reproducible results (vrs_segment_reduce).
 
-Rows that share a destination are reduced in one fixed order (include/vkradixsort_amd.h "K13"): the same input gives the same bits on
+Rows that share a destination are reduced in one fixed order (include/vkradixsort_amd_ops.h "K13"): the same input gives the same bits on
 every run, where torch's float atomics differ in the last bits from run to run.  The index forms sort (index, position) pairs by
 destination with the stable one-call sort, find every destination's range in the sorted indices with one search, and reduce the
 gathered rows range by range; nothing is added with a float atomic.  float16 and bfloat16 values are accumulated in float32 and rounded

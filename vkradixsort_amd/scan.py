@@ -1,7 +1,7 @@
 """torch.cumsum, cumprod, cummax and cummin drop-ins with a fixed order (vrs_scan_rows).
 
 A contiguous tensor is viewed as [S, L, C] around `dim` and scanned where it lies, every column on its own: no transposed copy for a dim
-other than the last.  Sums and products are combined in one fixed order (include/vkradixsort_amd.h "K14"), a function of the length
+other than the last.  Sums and products are combined in one fixed order (include/vkradixsort_amd_ops.h "K14"), a function of the length
 along dim, the width behind it, the dtype and VRS_TUNE_SCAN_TILE_ROWS alone: the same input gives the same bits on every run, which
 torch.cumsum on a GPU does not promise.  float16 and bfloat16 are accumulated in float32 and rounded once per output; a float sum starts
 at +0.0, so cumsum of [-0.0] is +0.0 (torch's CPU answer too).  cummax and cummin equal torch's CPU results bit for bit, indices included.

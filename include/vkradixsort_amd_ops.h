@@ -515,6 +515,16 @@ int vrs_scan_stats(vrs_context ctx, uint64_t *tile_calls, uint64_t *three_launch
  *   gather_out      R elements of value_bytes (1, 2, 4 or 8): gather_values[position], copied as bits (masked_select)
  *   scatter_out     n elements of value_bytes: out[i] = flag[i] ? scatter_source[rank(i)] : scatter_input[i], rank(i) the nonzero flags
  *                   in front of i (masked_scatter); scatter_source holds at least R elements, what lies behind R is never read
+ * THE ROW FORM (x[mask] and index_put with a mask over the leading dims): outputs->row_elems = W >= 2 makes every flag stand for a dense
+ * row of W elements of value_bytes; 0 and 1 both mean one element, the form above.  gather_values, scatter_input and scatter_out then
+ * hold n x W elements, gather_out R x W and scatter_source at least R x W: gather_out row r = gather_values row position(r), and
+ * scatter_out row i = flag[i] ? scatter_source row rank(i) : scatter_input row i.  flat and coords stay per flag and combine with the
+ * row outputs in one call.  n x W x value_bytes may pass 2^32 (byte offsets are 64-bit; 2^62 and more is refused); nothing from row
+ * num_selected on is written, no source row from there on is read; the size and overlap checks scale by W, the boundary stays the
+ * element's.  Two kernels of their own move the rows (the element kernels are not touched): a chunk's rows are one contiguous span of
+ * bytes that consecutive lanes copy word by word -- 16 bytes when the row's bytes and every base involved are multiples of 16, else the
+ * largest of 8, 4, 2 and 1 that divides them all -- over a grid of (tiles, slices), every slice ranking its chunk's flags again and
+ * copying its share of the span's words (csrc/vrs_compact_order.hpp: compact_row_word_bytes, compact_row_slices).
  * n < 2^32.  flags on its element's boundary (16-byte loads are used when it starts on a 16-byte boundary), scratch on a 16-byte
  * boundary and at least vrs_compact_scratch_bytes(n, T) bytes, value buffers on their element's boundary, int64 outputs on 8 bytes.
  * n == 0: VRS_OK, nothing enqueued but the count itself (0).  A NULL context, flags or scratch, an unknown dtype, layout or value_bytes,
@@ -535,7 +545,7 @@ typedef struct vrs_compact_outputs {
     vrs_buffer gather_values;  /* with gather_out: n elements of value_bytes */
     vrs_buffer gather_out;     /* NULL, or R elements of value_bytes */
     uint32_t value_bytes;      /* of gather_* and scatter_*: 1, 2, 4 or 8 */
-    uint32_t reserved;         /* 0 */
+    uint32_t row_elems;        /* 0 or 1: a flag stands for one element; W >= 2: for a row of W elements (THE ROW FORM) */
     vrs_buffer scatter_input;  /* with scatter_out: n elements */
     vrs_buffer scatter_source; /* with scatter_out: at least R elements (may be NULL when R is 0) */
     vrs_buffer scatter_out;    /* NULL, or n elements */
@@ -564,7 +574,7 @@ typedef struct vrs_compact_host_outputs {
     const void *gather_values;
     void *gather_out;
     uint32_t value_bytes;
-    uint32_t reserved;
+    uint32_t row_elems; /* as in vrs_compact_outputs; scatter_source_elems still counts elements: at least R x W of them */
     const void *scatter_input, *scatter_source;
     uint64_t scatter_source_elems;
     void *scatter_out;

@@ -19,14 +19,15 @@ scan       torch.cumsum / cumprod / cummax / cummin drop-ins: an inclusive prefi
            every run (cumsum, cumprod, cummax, cummin)
 compact    torch.nonzero / argwhere / where(condition) / count_nonzero / masked_select / masked_scatter drop-ins: ordered stream compaction
            in three phases that wait nowhere -- count, carries, emit (nonzero, argwhere, where, count_nonzero, masked_select,
-           masked_scatter)
+           masked_scatter); and x[mask] / index_put with a mask over the leading dims, every flag a whole row (mask_index,
+           mask_index_put)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
            for torch tensors)
 """
 from .binning import bincount, bincount_stats, histc, histogram  # noqa: F401
 from .capi import PushConstants, VrsError, load_library  # noqa: F401
-from .compact import (argwhere, compact_stats, count_nonzero, masked_scatter, masked_select, nonzero,  # noqa: F401
-                      where)
+from .compact import (argwhere, compact_stats, count_nonzero, mask_index, mask_index_put, masked_scatter,  # noqa: F401
+                      masked_select, nonzero, where)
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
 from .quantile import nanquantile, quantile, quantile_scratch_bytes, quantile_segments, quantile_stats  # noqa: F401

@@ -174,13 +174,13 @@ class CompactOutputs(ctypes.Structure):
     """vrs_compact_outputs: what vrs_compact_emit writes (include/vkradixsort_amd_ops.h "K15")."""
     _fields_ = [("num_selected", c_uint64), ("flat", c_void_p), ("coords", c_void_p), ("coords_layout", c_int), ("ndim", c_uint32),
                 ("shape", c_uint32 * 8), ("gather_values", c_void_p), ("gather_out", c_void_p), ("value_bytes", c_uint32),
-                ("reserved", c_uint32), ("scatter_input", c_void_p), ("scatter_source", c_void_p), ("scatter_out", c_void_p)]
+                ("row_elems", c_uint32), ("scatter_input", c_void_p), ("scatter_source", c_void_p), ("scatter_out", c_void_p)]
 
 
 class CompactHostOutputs(ctypes.Structure):
     """vrs_compact_host_outputs: the same on host pointers, for vrs_compact_host."""
     _fields_ = [("flat", c_void_p), ("coords", c_void_p), ("coords_layout", c_int), ("ndim", c_uint32), ("shape", c_uint32 * 8),
-                ("gather_values", c_void_p), ("gather_out", c_void_p), ("value_bytes", c_uint32), ("reserved", c_uint32),
+                ("gather_values", c_void_p), ("gather_out", c_void_p), ("value_bytes", c_uint32), ("row_elems", c_uint32),
                 ("scatter_input", c_void_p), ("scatter_source", c_void_p), ("scatter_source_elems", c_uint64), ("scatter_out", c_void_p)]
 
 

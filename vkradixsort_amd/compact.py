@@ -1,5 +1,5 @@
-"""torch.nonzero, argwhere, where(condition), count_nonzero, masked_select and masked_scatter drop-ins: ordered stream compaction
-(vrs_compact_count + vrs_compact_emit).
+"""torch.nonzero, argwhere, where(condition), count_nonzero, masked_select and masked_scatter drop-ins, and x[mask] / index_put for a mask
+over the leading dims (mask_index, mask_index_put): ordered stream compaction (vrs_compact_count + vrs_compact_emit).
 
 The flags are read in their own dtype (bool and the nine dtypes of the sort drop-ins; no `x != 0` pass), counted per tile, the counts
 scanned, and the survivors written in input order: positions, coordinates, gathered values, or the scatter form.  Outputs are integers
@@ -70,10 +70,12 @@ class _Counted:
             self.ctx.check(self.ctx.lib.vrs_compact_count(self.ctx.handle, f, n, self.code, s, c, ctypes.byref(got) if host else None))
         self.R = got.value if host else None
 
-    def emit(self, *, flat=None, coords=None, layout=capi.VRS_COMPACT_ROWS, shape=(), gather=None, gather_out=None, scatter=None):
-        """vrs_compact_emit into the given tensors; scatter = (input, source, out)."""
+    def emit(self, *, flat=None, coords=None, layout=capi.VRS_COMPACT_ROWS, shape=(), gather=None, gather_out=None, scatter=None,
+             row_elems=0, value_bytes=None):
+        """vrs_compact_emit into the given tensors; scatter = (input, source, out).  row_elems >= 2: the row form, every flag a row of
+        that many elements of value_bytes (the tensors' element size unless given)."""
         o = capi.CompactOutputs()
-        o.num_selected = self.R
+        o.num_selected, o.row_elems = self.R, row_elems
         inp, src, out = scatter or (None, None, None)
         value = gather if gather is not None else inp
         with buffers(self.ctx, self.flags, self.scratch, flat, coords, gather, gather_out, inp, src, out) as (f, s, *handles):
@@ -83,7 +85,7 @@ class _Counted:
                 o.ndim = len(shape)
                 o.shape = (ctypes.c_uint32 * 8)(*shape)
             o.gather_values, o.gather_out = gv, go
-            o.value_bytes = value.element_size() if value is not None else 0
+            o.value_bytes = value_bytes or (value.element_size() if value is not None else 0)
             o.scatter_input, o.scatter_source, o.scatter_out = si, ss, so
             self.ctx.check(self.ctx.lib.vrs_compact_emit(self.ctx.handle, f, self.n, self.code, s, ctypes.byref(o)))
 
@@ -202,4 +204,81 @@ def masked_scatter(x, mask, source):
         raise RuntimeError(f"masked_scatter: source has {source.numel()} elements, the mask sets {counted.R}")
     src = aligned(source.contiguous()).reshape(-1)
     counted.emit(scatter=(aligned(x.contiguous()).reshape(-1), src, out.reshape(-1)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- a mask over the leading dims: rows
+
+def _row_mask(name: str, x, mask):
+    """x and a bool mask over x's leading dims, refused as torch's indexing refuses them: (torch, the shape of one row)."""
+    import torch
+
+    if not isinstance(x, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        _refuse(f"{name} takes tensors")
+    if mask.dtype != torch.bool:
+        raise IndexError(f"{name}: the mask is a bool tensor, not {mask.dtype} (indexing by integer tensors is not offered)")
+    if mask.dim() > x.dim() or tuple(mask.shape) != tuple(x.shape[:mask.dim()]):
+        raise IndexError(f"{name}: the shape of the mask {list(mask.shape)} does not match the leading dims of the indexed tensor "
+                         f"{list(x.shape)}")
+    if x.element_size() not in (1, 2, 4, 8, 16):
+        _refuse(f"{name} takes elements of 1, 2, 4, 8 or 16 bytes")
+    return torch, tuple(x.shape[mask.dim():])
+
+
+def _row_width(name: str, x, tail):
+    """(value_bytes, row_elems) of one row of x: bits are copied, so an element of 16 bytes goes in as two of 8."""
+    value_bytes = min(x.element_size(), 8)
+    row_elems = x.element_size() // value_bytes
+    for size in tail:
+        row_elems *= size
+    if row_elems >= 1 << 32:
+        _refuse(f"{name} takes rows of fewer than 2^32 elements")
+    return value_bytes, row_elems
+
+
+def mask_index(x, mask):
+    """x[mask] on a GPU for a bool mask over x's leading dims (mask.shape == x.shape[:mask.dim()]): the rows of x under a set flag, in
+    order, as [R, *x.shape[mask.dim():]].  Every flag moves a whole row as dense words; a mask of x's own shape takes the element kernels, as masked_select.
+    Bits are copied (any dtype of 1, 2, 4, 8 or 16 bytes).  IndexError for a mask that is not bool or whose shape does not match, as
+    torch.  One host read of R, as torch makes.  Not offered: a mask over other dims (x[:, mask]), integer-tensor indices."""
+    torch, tail = _row_mask("mask_index", x, mask)
+    _on_gpu("mask_index", x, mask)
+    if mask.numel() == 0:
+        return torch.empty((0, *tail), dtype=x.dtype, device=x.device)
+    counted = _Counted("mask_index", mask, host=True)
+    out = torch.empty((counted.R, *tail), dtype=x.dtype, device=x.device)
+    if out.numel():
+        value_bytes, row_elems = _row_width("mask_index", x, tail)
+        counted.emit(gather=aligned(x.contiguous()).reshape(-1), gather_out=out.reshape(-1), row_elems=row_elems, value_bytes=value_bytes)
+    return out
+
+
+def mask_index_put(x, mask, values, accumulate: bool = False):
+    """torch.index_put(x, (mask,), values) on a GPU, out of place, for a bool mask over x's leading dims: a copy of x whose rows under a
+    set flag are the rows of values in order.  values of exactly [R, *x.shape[mask.dim():]] and contiguous is read where it lies;
+    anything else that broadcasts to that shape is expanded first, and what does not is a RuntimeError.  Not offered: accumulate=True,
+    the in-place x[mask] = values."""
+    torch, tail = _row_mask("mask_index_put", x, mask)
+    if accumulate:
+        _refuse("mask_index_put takes no accumulate=True")
+    if not isinstance(values, torch.Tensor):
+        values = torch.as_tensor(values, dtype=x.dtype, device=x.device)
+    if values.dtype != x.dtype:
+        raise RuntimeError(f"mask_index_put: expected self and values to have same dtypes but got {x.dtype} and {values.dtype}")
+    shape = tuple(values.shape)
+    if len(shape) > len(tail) + 1 or any(v not in (1, t) for v, t in zip(reversed(shape), reversed(tail))):
+        raise RuntimeError(f"mask_index_put: values of shape {list(shape)} do not broadcast to [R, {', '.join(map(str, tail))}]")
+    _on_gpu("mask_index_put", x, mask, values)
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    if x.numel() == 0:
+        return out
+    counted = _Counted("mask_index_put", mask, host=True)
+    target = (counted.R, *tail)
+    if len(shape) == len(target) and shape[0] not in (1, counted.R):
+        raise RuntimeError(f"mask_index_put: values of shape {list(shape)} do not broadcast to {list(target)}")
+    if shape != target or not values.is_contiguous():
+        values = values.expand(target).contiguous()
+    value_bytes, row_elems = _row_width("mask_index_put", x, tail)
+    counted.emit(scatter=(aligned(x.contiguous()).reshape(-1), aligned(values).reshape(-1), out.reshape(-1)),
+                 row_elems=row_elems, value_bytes=value_bytes)
     return out

@@ -52,8 +52,22 @@ uint64_t host_bits(const void *flags, uint64_t i) {
     return static_cast<const W *>(flags)[i];
 }
 
-void host_copy(void *dst, uint64_t to, const void *src, uint64_t from, uint32_t value_bytes) {
-    std::memcpy(static_cast<char *>(dst) + to * value_bytes, static_cast<const char *>(src) + from * value_bytes, value_bytes);
+// row `to` of dst = row `from` of src, rows of row_bytes (one element, or the row form's W elements), word by word as the kernels copy it
+void host_copy(void *dst, uint64_t to, const void *src, uint64_t from, uint64_t row_bytes, uint32_t word_bytes) {
+    char *d = static_cast<char *>(dst) + to * row_bytes;
+    const char *s = static_cast<const char *>(src) + from * row_bytes;
+    for (uint64_t w = 0; w < row_bytes; w += word_bytes) std::memcpy(d + w, s + w, word_bytes);
+}
+
+uint64_t address(const void *p) { return reinterpret_cast<uintptr_t>(p); }
+
+// the elements one flag stands for: row_elems, where 0 says what 1 says
+uint64_t row_width(uint32_t row_elems) { return row_elems >= 2u ? row_elems : 1u; }
+
+// n x W x value_bytes, or false when that passes 2^62 (no buffer is that large, and nothing wraps)
+bool row_form_bytes(uint64_t n, uint64_t W, uint32_t value_bytes, uint64_t *row_bytes) {
+    *row_bytes = W * value_bytes;  // (below 2^35)
+    return (static_cast<unsigned __int128>(n) * *row_bytes >> 62) == 0u;
 }
 
 }  // namespace
@@ -104,6 +118,12 @@ int vrs_compact_host(const void *flags, uint64_t n, int dtype, const vrs_compact
         return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "compact: value_bytes is 1, 2, 4 or 8");
     if (n != 0u && ((o.gather_out && !o.gather_values) || (o.scatter_out && !o.scatter_input)))
         return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "compact: gather_values or scatter_input is NULL");
+    const uint64_t W = row_width(o.row_elems);
+    uint64_t row_bytes = 0u;
+    if ((o.gather_out || o.scatter_out) && !row_form_bytes(n, W, o.value_bytes, &row_bytes))
+        return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "compact: n x row_elems x value_bytes is below 2^62");
+    const uint32_t gather_word = vrs::compact_row_word_bytes(row_bytes, address(o.gather_values) | address(o.gather_out));
+    const uint32_t scatter_word = vrs::compact_row_word_bytes(row_bytes, address(o.scatter_input) | address(o.scatter_source) | address(o.scatter_out));
     const uint64_t keep = vrs::compact_keep_mask(dtype);
     const int bytes = vrs::compact_dtype_bytes(dtype);
     auto set = [&](uint64_t i) {
@@ -114,20 +134,20 @@ int vrs_compact_host(const void *flags, uint64_t n, int dtype, const vrs_compact
     uint64_t R = 0u;
     for (uint64_t i = 0; i < n; ++i) R += set(i) ? 1u : 0u;
     if (out_count) *out_count = R;
-    if (o.scatter_out && (o.scatter_source_elems < R || (R != 0u && !o.scatter_source)))
-        return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "compact: scatter_source holds fewer elements than flags are nonzero");
+    if (o.scatter_out && (o.scatter_source_elems / W < R || (R != 0u && !o.scatter_source)))
+        return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "compact: scatter_source holds fewer elements (rows of row_elems) than flags are nonzero");
     const vrs::CompactShape shape = o.coords && n != 0u ? vrs::compact_shape_make(o.ndim, o.shape) : vrs::CompactShape{};
     uint64_t row = 0u;
     for (uint64_t i = 0; i < n; ++i) {
         const bool s = set(i);
-        if (o.scatter_out) host_copy(o.scatter_out, i, s ? o.scatter_source : o.scatter_input, s ? row : i, o.value_bytes);
+        if (o.scatter_out) host_copy(o.scatter_out, i, s ? o.scatter_source : o.scatter_input, s ? row : i, row_bytes, scatter_word);
         if (!s) continue;
         const uint32_t p = static_cast<uint32_t>(i);
         if (o.flat) o.flat[row] = static_cast<int64_t>(p);
         if (o.coords)
             for (uint32_t k = 0; k < o.ndim; ++k)
                 o.coords[o.coords_layout == VRS_COMPACT_ROWS ? row * o.ndim + k : k * R + row] = static_cast<int64_t>(vrs::compact_coordinate(p, shape, k));
-        if (o.gather_out) host_copy(o.gather_out, row, o.gather_values, i, o.value_bytes);
+        if (o.gather_out) host_copy(o.gather_out, row, o.gather_values, i, row_bytes, gather_word);
         ++row;
     }
     return VRS_OK;
@@ -183,8 +203,11 @@ int vrs_compact_emit(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, v
     if (o.coords && (rc = check_shape(ctx, n, o.ndim, o.shape))) return rc;
     if ((o.gather_out || o.scatter_out) && !vrs::compact_value_bytes_known(o.value_bytes))
         return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "compact: value_bytes is 1, 2, 4 or 8");
+    uint64_t row_bytes = 0u;
+    if ((o.gather_out || o.scatter_out) && !row_form_bytes(n, row_width(o.row_elems), o.value_bytes, &row_bytes))
+        return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "compact: n x row_elems x value_bytes is below 2^62");
     if (n == 0u) return VRS_OK;
-    const size_t vb = o.value_bytes, flag_bytes = static_cast<size_t>(n) * static_cast<size_t>(vrs::compact_dtype_bytes(dtype));
+    const size_t vb = o.value_bytes, rb = row_bytes, flag_bytes = static_cast<size_t>(n) * static_cast<size_t>(vrs::compact_dtype_bytes(dtype));
     // every output: (buffer, bytes it must hold, its boundary); an output of no bytes (R == 0) needs no buffer and is left out
     struct Out {
         vrs_buffer buf;
@@ -193,11 +216,11 @@ int vrs_compact_emit(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, v
     };
     const Out outs[4] = {{o.flat, static_cast<size_t>(R) * 8u, 8u, "flat"},
                          {o.coords, static_cast<size_t>(R) * 8u * (o.coords ? o.ndim : 0u), 8u, "coords"},
-                         {o.gather_out, static_cast<size_t>(R) * vb, vb, "gather_out"},
-                         {o.scatter_out, static_cast<size_t>(n) * vb, vb, "scatter_out"}};
-    const Out ins[3] = {{o.gather_out ? o.gather_values : nullptr, static_cast<size_t>(n) * vb, vb, "gather_values"},
-                        {o.scatter_out ? o.scatter_input : nullptr, static_cast<size_t>(n) * vb, vb, "scatter_input"},
-                        {o.scatter_out ? o.scatter_source : nullptr, static_cast<size_t>(R) * vb, vb, "scatter_source"}};
+                         {o.gather_out, static_cast<size_t>(R) * rb, vb, "gather_out"},
+                         {o.scatter_out, static_cast<size_t>(n) * rb, vb, "scatter_out"}};
+    const Out ins[3] = {{o.gather_out ? o.gather_values : nullptr, static_cast<size_t>(n) * rb, vb, "gather_values"},
+                        {o.scatter_out ? o.scatter_input : nullptr, static_cast<size_t>(n) * rb, vb, "scatter_input"},
+                        {o.scatter_out ? o.scatter_source : nullptr, static_cast<size_t>(R) * rb, vb, "scatter_source"}};
     for (const Out &x : outs) {
         if (!x.buf || x.bytes == 0u) continue;
         if ((rc = check_buffer(ctx, x.buf, x.bytes, x.name))) return rc;
@@ -235,12 +258,15 @@ int vrs_compact_emit(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, v
         a.gather_out = o.gather_out ? o.gather_out->ptr : nullptr;
     }
     a.value_bytes = o.value_bytes;
+    vrs::CompactRowForm rows{};
+    rows.row_elems = o.row_elems;
+    if (const char *v = std::getenv("VRS_COMPACT_ROW_SLICE_BYTES")) rows.slice_bytes = std::strtoull(v, nullptr, 10);  // (the timing tool's sweep)
     if (o.scatter_out) {
         a.scatter_input = o.scatter_input->ptr;
         a.scatter_source = R != 0u ? o.scatter_source->ptr : nullptr;
         a.scatter_out = o.scatter_out->ptr;
     }
-    VRS_HIP(ctx, vrs::launch_compact_emit(ctx->stream, a));
+    VRS_HIP(ctx, vrs::launch_compact_emit(ctx->stream, a, rows));
     ++ctx->compact_calls[1];
     return VRS_OK;
 }

@@ -6,6 +6,8 @@
 //            lane's vector, across the lanes of a wave, across waves and rounds through LDS), the survivors' positions staged in LDS in
 //            output order, then dense stores -- consecutive lanes write consecutive output words.  The scatter form stages every
 //            element's source index instead and writes all n outputs.
+//   rows     the row form's emit (a flag stands for a row of W >= 2 elements): kernels of their own over (tiles, slices) that rank and
+//            stage the same way and then copy a chunk's rows as one contiguous span of words.
 // The rules (predicate, tiles, coordinates): vrs_compact_order.hpp.
 #include "vrs_compact.hpp"
 
@@ -274,6 +276,155 @@ __global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(Compac
     }
 }
 
+// ---------------------------------------------------------------------------------------------- rows
+
+// The row form (row_elems = W >= 2): a flag stands for a row of row_bytes bytes, and what a chunk writes is one contiguous span of bytes
+// -- its survivors' rows (gather), or all of its rows (scatter).  Consecutive lanes take consecutive words of the span, so stores are
+// dense whatever the mask is, and loads are dense inside every row.  The word: compact_row_word_bytes.
+struct CompactRowArgs {
+    uint64_t row_bytes, words_per_row, slice_bytes;
+    CompactDiv by_words;  // words_per_row as a divisor, for rows of at most kCompactRowNarrowWords words
+    uint32_t word_bytes, pad;
+};
+
+CompactRowArgs compact_row_args(const CompactEmitArgs &a, const CompactRowForm &form, uint64_t bases) {
+    CompactRowArgs r{};
+    r.row_bytes = static_cast<uint64_t>(form.row_elems) * a.value_bytes;
+    r.word_bytes = compact_row_word_bytes(r.row_bytes, bases);
+    r.words_per_row = r.row_bytes / r.word_bytes;
+    r.by_words = compact_div_make(r.words_per_row <= kCompactRowNarrowWords ? static_cast<uint32_t>(r.words_per_row) : 1u);
+    r.slice_bytes = form.slice_bytes ? form.slice_bytes : kCompactRowSliceBytes;
+    return r;
+}
+
+// dst[e] = *src_of(e) for the words e = first, first + stride, ... below `words`; four loads of a lane are in flight before its stores
+template <class W, class Src>
+__device__ inline void copy_words(W *dst, uint64_t words, uint64_t first, uint64_t stride, Src src_of) {
+    uint64_t e = first;
+    for (; e + 3u * stride < words; e += 4u * stride) {
+        const uint64_t e1 = e + stride, e2 = e1 + stride, e3 = e2 + stride;
+        const W v0 = *src_of(e), v1 = *src_of(e1), v2 = *src_of(e2), v3 = *src_of(e3);
+        dst[e] = v0, dst[e1] = v1, dst[e2] = v2, dst[e3] = v3;
+    }
+    for (; e < words; e += stride) dst[e] = *src_of(e);
+}
+
+// `rows` rows from dst on, row j copied from row_of(j): as one span of rows x words_per_row words cut by the constant division while that
+// index fits 32 bits, row by row with a 64-bit word index for wider rows.  This workgroup's lanes take the words first + k x stride.
+template <class W, class Row>
+__device__ inline void copy_rows(char *dst, uint32_t rows, const CompactRowArgs &r, uint64_t first, uint64_t stride, Row row_of) {
+    if (r.words_per_row <= kCompactRowNarrowWords) {
+        const uint32_t wpr = static_cast<uint32_t>(r.words_per_row);
+        copy_words(reinterpret_cast<W *>(dst), static_cast<uint64_t>(rows) * wpr, first, stride, [&](uint64_t e) {  // (at most 2^32 words: e < 2^32)
+            const uint32_t j = compact_div(static_cast<uint32_t>(e), r.by_words), w = static_cast<uint32_t>(e) - j * wpr;
+            return reinterpret_cast<const W *>(row_of(j)) + w;
+        });
+    } else {
+        for (uint32_t j = 0u; j < rows; ++j) {
+            const W *src = reinterpret_cast<const W *>(row_of(j));
+            copy_words(reinterpret_cast<W *>(dst + j * r.row_bytes), r.words_per_row, first, stride, [&](uint64_t w) { return src + w; });
+        }
+    }
+}
+
+template <class Row>
+__device__ inline void copy_rows_as(char *dst, uint32_t rows, const CompactRowArgs &r, uint64_t first, uint64_t stride, Row row_of) {
+    switch (r.word_bytes) {
+        case 16u: copy_rows<uint4>(dst, rows, r, first, stride, row_of); break;
+        case 8u: copy_rows<uint64_t>(dst, rows, r, first, stride, row_of); break;
+        case 4u: copy_rows<uint32_t>(dst, rows, r, first, stride, row_of); break;
+        case 2u: copy_rows<uint16_t>(dst, rows, r, first, stride, row_of); break;
+        default: copy_rows<uint8_t>(dst, rows, r, first, stride, row_of); break;
+    }
+}
+
+// gather_out row r = gather_values row position(r).  Grid (tiles, slices); a tile without survivors is skipped, and so are the slices
+// its survivors do not need (a sparse tile moves few bytes, and every slice reads the tile's flags).
+template <int BYTES>
+__global__ __launch_bounds__(kCompactThreads) void compact_gather_rows_kernel(CompactEmitArgs a, CompactRowArgs r, uint64_t keep, uint32_t tiles) {
+    constexpr uint32_t EPV = 16u / BYTES;
+    __shared__ uint32_t stage[kCompactChunk];
+    __shared__ uint32_t wave_total[BYTES][kCompactThreads / 64u];
+    const uint32_t tid = threadIdx.x;
+    const TileSpan span = tile_span(a.scratch, blockIdx.x, tiles);
+    if (span.count == 0u) return;
+    const uint32_t want = compact_row_slices_for(span.count, r.row_bytes, r.slice_bytes), slices = want < gridDim.y ? want : gridDim.y;
+    if (blockIdx.y >= slices) return;  // (the same in every lane)
+    const uint64_t first = static_cast<uint64_t>(blockIdx.y) * kCompactThreads + tid, stride = static_cast<uint64_t>(slices) * kCompactThreads;
+    const char *flags = static_cast<const char *>(a.flags), *values = static_cast<const char *>(a.gather_values);
+    const bool aligned16 = (reinterpret_cast<uintptr_t>(flags) & 15u) == 0u;
+    const uint64_t tbase = static_cast<uint64_t>(blockIdx.x) * a.T;
+    uint32_t done = 0u;
+    for (uint32_t c = 0u; c < a.T && done < span.count; c += kCompactChunk) {
+        const uint64_t cbase = tbase + c;
+        uint32_t mask[BYTES], slot[BYTES];
+        const uint32_t total = rank_chunk<BYTES>(flags, aligned16, cbase, a.n, keep, wave_total, mask, slot);
+#pragma unroll
+        for (int k = 0; k < BYTES; ++k) {
+            const uint32_t p0 = static_cast<uint32_t>(cbase + static_cast<uint64_t>(k) * (kCompactThreads * EPV) + tid * EPV);
+            uint32_t m = mask[k], at = slot[k];
+            while (m) {
+                stage[at++] = p0 + static_cast<uint32_t>(__ffs(m) - 1);
+                m &= m - 1u;
+            }
+        }
+        __syncthreads();
+        const uint64_t row0 = static_cast<uint64_t>(span.first) + done;
+        if (row0 < a.limit) {  // (no output row from limit on is written)
+            const uint64_t room = a.limit - row0;
+            const uint32_t rows = room < total ? static_cast<uint32_t>(room) : total;
+            copy_rows_as(static_cast<char *>(a.gather_out) + row0 * r.row_bytes, rows, r, first, stride,
+                         [&](uint32_t j) { return values + stage[j] * r.row_bytes; });
+        }
+        done += total;
+        __syncthreads();
+    }
+}
+
+// scatter_out row i = flag[i] ? scatter_source row rank(i) : scatter_input row i.  Grid (tiles, slices); every slice has work.
+template <int BYTES>
+__global__ __launch_bounds__(kCompactThreads) void compact_scatter_rows_kernel(CompactEmitArgs a, CompactRowArgs r, uint64_t keep, uint32_t tiles) {
+    constexpr uint32_t EPV = 16u / BYTES;
+    __shared__ uint32_t stage[kCompactChunk];
+    __shared__ uint32_t wave_total[BYTES][kCompactThreads / 64u];
+    const uint32_t tid = threadIdx.x;
+    const TileSpan span = tile_span(a.scratch, blockIdx.x, tiles);
+    const uint64_t first = static_cast<uint64_t>(blockIdx.y) * kCompactThreads + tid, stride = static_cast<uint64_t>(gridDim.y) * kCompactThreads;
+    const char *flags = static_cast<const char *>(a.flags), *source = static_cast<const char *>(a.scatter_source);
+    const bool aligned16 = (reinterpret_cast<uintptr_t>(flags) & 15u) == 0u;
+    const uint64_t tbase = static_cast<uint64_t>(blockIdx.x) * a.T;
+    uint32_t done = 0u;
+    for (uint32_t c = 0u; c < a.T; c += kCompactChunk) {
+        const uint64_t cbase = tbase + c;
+        if (cbase >= a.n) break;
+        uint32_t mask[BYTES], slot[BYTES];
+        const uint32_t total = rank_chunk<BYTES>(flags, aligned16, cbase, a.n, keep, wave_total, mask, slot);
+#pragma unroll
+        for (int k = 0; k < BYTES; ++k) {
+            const uint32_t at = static_cast<uint32_t>(k) * (kCompactThreads * EPV) + tid * EPV;
+            uint32_t rank = span.first + done + slot[k];
+#pragma unroll
+            for (uint32_t b = 0u; b < EPV; ++b) {
+                const bool set = (mask[k] >> b) & 1u;
+                stage[at + b] = set ? rank : kNone;
+                rank += set ? 1u : 0u;
+            }
+        }
+        __syncthreads();
+        const uint64_t left = a.n - cbase;
+        const uint32_t len = left < kCompactChunk ? static_cast<uint32_t>(left) : kCompactChunk;
+        const char *input = static_cast<const char *>(a.scatter_input) + cbase * r.row_bytes;
+        copy_rows_as(static_cast<char *>(a.scatter_out) + cbase * r.row_bytes, len, r, first, stride, [&](uint32_t j) {
+            const uint32_t s = stage[j];
+            return s != kNone && s < a.limit ? source + s * r.row_bytes : input + j * r.row_bytes;  // (no source row from limit on is read)
+        });
+        done += total;
+        __syncthreads();
+    }
+}
+
+uint64_t address(const void *p) { return reinterpret_cast<uintptr_t>(p); }
+
 template <int BYTES>
 hipError_t count_as(hipStream_t stream, const CompactCountArgs &a, uint32_t tiles) {
     uint32_t *words = reinterpret_cast<uint32_t *>(a.scratch + kCompactHeaderBytes);
@@ -286,13 +437,27 @@ hipError_t count_as(hipStream_t stream, const CompactCountArgs &a, uint32_t tile
 }
 
 template <int BYTES>
-hipError_t emit_as(hipStream_t stream, const CompactEmitArgs &a, uint32_t tiles) {
+hipError_t emit_as(hipStream_t stream, const CompactEmitArgs &a, const CompactRowForm &form, uint32_t tiles) {
     const uint64_t keep = compact_keep_mask(a.dtype);
-    if (a.flat || a.coords || a.gather_out) {
-        hipLaunchKernelGGL(compact_emit_kernel<BYTES>, dim3(tiles), dim3(kCompactThreads), 0, stream, a, keep, tiles, compact_div_make(a.shape.ndim));
+    const bool rows = form.row_elems >= 2u;
+    if (a.flat || a.coords || (a.gather_out && !rows)) {
+        CompactEmitArgs e = a;
+        if (rows) e.gather_values = nullptr, e.gather_out = nullptr;  // (positions stay per flag; the rows have a kernel of their own)
+        hipLaunchKernelGGL(compact_emit_kernel<BYTES>, dim3(tiles), dim3(kCompactThreads), 0, stream, e, keep, tiles, compact_div_make(a.shape.ndim));
         if (const hipError_t e = hipGetLastError()) return e;
     }
-    if (a.scatter_out) {
+    if (a.gather_out && rows) {
+        const CompactRowArgs r = compact_row_args(a, form, address(a.gather_values) | address(a.gather_out));
+        const uint32_t slices = compact_row_slices_for(a.n < a.T ? a.n : a.T, r.row_bytes, r.slice_bytes);
+        hipLaunchKernelGGL(compact_gather_rows_kernel<BYTES>, dim3(tiles, slices), dim3(kCompactThreads), 0, stream, a, r, keep, tiles);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    if (a.scatter_out && rows) {
+        const CompactRowArgs r = compact_row_args(a, form, address(a.scatter_input) | address(a.scatter_source) | address(a.scatter_out));
+        const uint32_t slices = compact_row_slices_for(a.n < a.T ? a.n : a.T, r.row_bytes, r.slice_bytes);
+        hipLaunchKernelGGL(compact_scatter_rows_kernel<BYTES>, dim3(tiles, slices), dim3(kCompactThreads), 0, stream, a, r, keep, tiles);
+        if (const hipError_t e = hipGetLastError()) return e;
+    } else if (a.scatter_out) {
         hipLaunchKernelGGL(compact_scatter_kernel<BYTES>, dim3(tiles), dim3(kCompactThreads), 0, stream, a, keep, tiles);
         if (const hipError_t e = hipGetLastError()) return e;
     }
@@ -311,13 +476,13 @@ hipError_t launch_compact_count(hipStream_t stream, const CompactCountArgs &a) {
     }
 }
 
-hipError_t launch_compact_emit(hipStream_t stream, const CompactEmitArgs &a) {
+hipError_t launch_compact_emit(hipStream_t stream, const CompactEmitArgs &a, const CompactRowForm &rows) {
     const uint32_t tiles = compact_tiles(a.n, a.T);
     switch (compact_dtype_bytes(a.dtype)) {
-        case 1: return emit_as<1>(stream, a, tiles);
-        case 2: return emit_as<2>(stream, a, tiles);
-        case 4: return emit_as<4>(stream, a, tiles);
-        default: return emit_as<8>(stream, a, tiles);
+        case 1: return emit_as<1>(stream, a, rows, tiles);
+        case 2: return emit_as<2>(stream, a, rows, tiles);
+        case 4: return emit_as<4>(stream, a, rows, tiles);
+        default: return emit_as<8>(stream, a, rows, tiles);
     }
 }
 

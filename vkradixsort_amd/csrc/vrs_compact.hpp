@@ -48,7 +48,15 @@ struct CompactEmitArgs {
     void *scatter_out;                           // [n]
 };
 
+// The row form, beside CompactEmitArgs (which the element kernels take as it always was): row_elems of 0 or 1 leaves everything to them;
+// W >= 2 makes gather_* and scatter_* rows of W elements, moved by the row kernels.  slice_bytes: 0 for kCompactRowSliceBytes, or what
+// stands in for it (the timing tool's sweep).
+struct CompactRowForm {
+    uint32_t row_elems, pad;
+    uint64_t slice_bytes;
+};
+
 hipError_t launch_compact_count(hipStream_t stream, const CompactCountArgs &a);
-hipError_t launch_compact_emit(hipStream_t stream, const CompactEmitArgs &a);
+hipError_t launch_compact_emit(hipStream_t stream, const CompactEmitArgs &a, const CompactRowForm &rows);
 
 }  // namespace vrs

@@ -64,6 +64,33 @@ __host__ __device__ inline uint32_t compact_div(uint32_t a, const CompactDiv &c)
 }
 __host__ __device__ inline uint32_t compact_mod(uint32_t a, const CompactDiv &c) { return a - compact_div(a, c) * c.d; }
 
+// THE ROW FORM (row_elems = W >= 2): every flag stands for a dense row of row_bytes = W x value_bytes bytes, and a chunk's output is one
+// contiguous span of bytes that consecutive lanes copy word by word.  THE WORD: 16 bytes when row_bytes and every base involved (the
+// values and the output of a gather; the input, the source and the output of a scatter, or-ed into `bases`) are multiples of 16, else the
+// largest of 8, 4, 2 and 1 bytes that divides them all -- so every row of every buffer starts on a word.
+__host__ __device__ inline uint32_t compact_row_word_bytes(uint64_t row_bytes, uint64_t bases) {
+    const uint64_t all = row_bytes | bases;
+    uint32_t word = 16u;
+    while (all & (word - 1u)) word >>= 1;
+    return word;
+}
+// A chunk's span is indexed in 32 bits and cut into rows by compact_div while a row holds at most kCompactRowNarrowWords words
+// (kCompactChunk rows of them are at most 2^32 words); wider rows are walked one by one with a 64-bit word index.
+constexpr uint64_t kCompactRowNarrowWords = 1ull << 20;
+// The row kernels run over (tiles, slices): every slice ranks its chunks' flags again (one flag per row) and copies every slices-th run
+// of kCompactThreads words of the span.  slices = the bytes a full tile moves over kCompactRowSliceBytes, at most kCompactRowSlicesMax.
+// kCompactRowSliceBytes is a FIRST SETTING, NOT A CROSSOVER: nobody has measured it (tools/mask_index_time.py sweeps it through
+// VRS_COMPACT_ROW_SLICE_BYTES when it is given a device).
+constexpr uint64_t kCompactRowSliceBytes = 256u * 1024u;
+constexpr uint32_t kCompactRowSlicesMax = 2048u;
+__host__ __device__ inline uint32_t compact_row_slices_for(uint64_t rows, uint64_t row_bytes, uint64_t slice_bytes) {
+    const uint64_t want = (rows * row_bytes + slice_bytes - 1u) / slice_bytes;  // (rows <= 65536, row_bytes < 2^35: no wrap)
+    return want < 1u ? 1u : want > kCompactRowSlicesMax ? kCompactRowSlicesMax : static_cast<uint32_t>(want);
+}
+__host__ __device__ inline uint32_t compact_row_slices(uint64_t n, uint32_t T, uint64_t row_bytes) {
+    return compact_row_slices_for(n < T ? n : T, row_bytes, kCompactRowSliceBytes);
+}
+
 // A flat position in a contiguous array of `ndim` sizes: coordinate k = (p / stride[k]) mod size[k], stride[k] the product of the sizes
 // behind k.  Every stride and size is at most n < 2^32.
 struct CompactShape {

@@ -1,6 +1,7 @@
 """The torch drop-ins interleaved on the contexts `_torch.context_for` hands out, default tunings (kept pool layouts included):
-tools/fuzz_ops.py's committed runs -- every element of every output against torch on the CPU and numpy, no tolerance --, and the
-kept-layout scenario spelled out.  tests/test_ops_fuzz_cpu.py (no device) holds the same runs to what the generator claims to reach."""
+tools/fuzz_ops.py's committed runs of both decks -- every element of every output against torch on the CPU and numpy, no tolerance but
+the stated bound of the newer deck's float sums and products --, and the kept-layout scenario spelled out.  tests/test_ops_fuzz_cpu.py (no
+device) holds the same runs to what the generator claims to reach."""
 import ctypes
 import importlib.util
 from pathlib import Path
@@ -37,6 +38,13 @@ def pool_layouts(ctx):
 @pytest.mark.parametrize("seed,count", fuzz.COMMITTED_RUNS)
 def test_the_committed_runs_pass(seed, count):
     assert fuzz.run(seed, count, "cuda:0") == count
+
+
+@pytest.mark.parametrize("seed,count", fuzz.COMMITTED_RUNS_NEWER)
+def test_the_committed_runs_of_the_newer_deck_pass(seed, count):
+    """The selections, counts, reductions, scans and compactions between the first deck's ops, a deferred sort pending before every second
+    window's newer ops: bits where the result is defined exactly, the stated bound of the term count where it is a float sum or product."""
+    assert fuzz.run(seed, count, "cuda:0", deck="newer") == count
 
 
 def test_a_kept_layout_meets_other_values_between_other_ops(capsys):

@@ -53,9 +53,34 @@ def _refusal_dtypes(fn) -> set:
 def accepted_dtypes() -> dict:
     nine = {str(d).split(".")[1] for d in NINE if _accepts_sort(d)}
     assert nine == _refusal_dtypes(sort_mod._dtype_code)
-    return {"sort": nine, "sort_values": nine, "argsort": nine, "searchsorted": nine, "bucketize": nine,
+    return {**{op: {name for name in fuzz.TEN if _wrapper_takes(op, name)} for op in fuzz.NEWER_OPS}, "sort": nine, "sort_values": nine, "argsort": nine, "searchsorted": nine, "bucketize": nine,
             "sort_rows": _refusal_dtypes(segmented_mod.sort_rows), "topk": _refusal_dtypes(topk_mod.topk),
             "unique": _refusal_dtypes(unique_mod._check_tensor), "unique_consecutive": _refusal_dtypes(unique_mod._check_tensor)}
+
+
+def _wrapper_takes(op: str, name: str) -> bool:
+    """Whether a newer wrapper takes the dtype, by its own refusals: called with small CPU tensors of the dtype, a wrapper that takes it
+    gets as far as refusing tensors that are not on a GPU; one that does not refuses the dtype first, in whatever words it has for that.
+    cumsum and cumprod take every real dtype (what the kernel does not write is converted first), so among the ten candidates their
+    set is the ten; that the probe can say no there too is asserted with a complex dtype and, for cummax / cummin, a dtype without a code."""
+    x = torch.zeros(4, dtype=getattr(torch, name))
+    index, mask = torch.zeros(4, dtype=torch.int64), torch.ones(4, dtype=torch.bool)
+    calls = {"kthvalue": lambda: vrs.kthvalue(x, 1), "median": lambda: vrs.median(x, 0), "nanmedian": lambda: vrs.nanmedian(x, 0),
+             "quantile": lambda: vrs.quantile(x, 0.5), "nanquantile": lambda: vrs.nanquantile(x, 0.5), "bincount": lambda: vrs.bincount(x),
+             "histc": lambda: vrs.histc(x), "histogram": lambda: vrs.histogram(x, 2),
+             "segment_reduce": lambda: vrs.segment_reduce(x, "max", lengths=torch.tensor([4])), "index_add": lambda: vrs.index_add(x, 0, index, x),
+             "index_reduce": lambda: vrs.index_reduce(x, 0, index, x, "amax"), "scatter_reduce": lambda: vrs.scatter_reduce(x, 0, index, x, "amax"),
+             "cumsum": lambda: vrs.cumsum(x, 0), "cumprod": lambda: vrs.cumprod(x, 0), "cummax": lambda: vrs.cummax(x, 0), "cummin": lambda: vrs.cummin(x, 0),
+             "nonzero": lambda: vrs.nonzero(x), "argwhere": lambda: vrs.argwhere(x), "count_nonzero": lambda: vrs.count_nonzero(x),
+             "masked_select": lambda: vrs.masked_select(x, mask), "masked_scatter": lambda: vrs.masked_scatter(x, mask, x),
+             "mask_index": lambda: vrs.mask_index(x, mask), "mask_index_put": lambda: vrs.mask_index_put(x, mask, x)}
+    try:
+        calls[op]()
+    except vrs.VrsError as e:
+        return "on a GPU" in str(e)
+    except RuntimeError:
+        return False
+    raise AssertionError(f"{op} took CPU tensors")
 
 
 def _accepts_sort(dtype) -> bool:
@@ -174,7 +199,7 @@ def test_every_op_and_dtype_the_wrappers_accept_occurs(all_cases):
     accepted = accepted_dtypes()
     assert {op: set(d) for op, d in fuzz.OP_DTYPES.items()} == accepted
     seen = {(c["op"], c["dtype"]) for c in all_cases if c.get("variant") not in ("mixed", "dependent")}
-    missing = {(op, dt) for op, dts in accepted.items() for dt in dts} - seen
+    missing = {(op, dt) for op in fuzz.FIRST_OPS for dt in accepted[op]} - seen  # (the newer ops: the newer deck's run, below)
     assert not missing, sorted(missing)
 
 
@@ -348,3 +373,474 @@ def test_no_case_leaves_an_ops_documented_domain(all_cases):
                 assert len(c["seq_shape"]) == 1 and "sorter" not in c and "side" not in c and c["dtype"] == c["in_dtype"], c
             else:
                 assert not (c["side"] == "left" and c["right"]), c
+
+
+# ==== the newer deck ==============================================================================================================
+# the same claims for the committed run of deck "newer", and two that need no device either: torch's own CPU functions pass the fuzz's
+# checks (the references and their bounds are right), and one changed element does not (they would notice).
+
+scan_mod = importlib.import_module("vkradixsort_amd.scan")
+FIRST_DECK_SHA256 = "8be40a9da0caad19ab49ab6ad19f6cd2b2add9c492a6b967ef1872ca5c491b6f"  # json.dumps(list(cases(104, 256)), sort_keys=True)
+
+
+@pytest.fixture(scope="module")
+def newer_cases():
+    return [c for seed, count in fuzz.COMMITTED_RUNS_NEWER for c in fuzz.cases(seed, count, deck="newer")]
+
+
+def test_the_first_decks_stream_is_what_it_was_before_the_newer_deck():
+    import hashlib
+    import json
+    assert hashlib.sha256(json.dumps(list(fuzz.cases(104, 256)), sort_keys=True).encode()).hexdigest() == FIRST_DECK_SHA256
+    assert fuzz.COMMITTED_RUNS == [(104, 256)]
+
+
+def _scan_kernel_dtypes(case):
+    """(what the kernel reads, what it writes) for a scan case, by scan._arith's own rule."""
+    name = case["dtype"]
+    if case["op"] in ("cummax", "cummin"):
+        name = "uint8" if name == "bool" else name
+        return name, name
+    target = case["out_dtype"] or (name if name in fuzz.FLOATS else "int64")
+    if target in scan_mod._KERNEL_OUT:
+        direct = name == target or (target == "int64" and name in scan_mod._WIDENED)
+        return (name if direct else target), target
+    if target in fuzz.FLOATS:
+        return "float32", "float32"
+    return (target if target in scan_mod._WIDENED else "int64"), "int64"
+
+
+def _sizes(case):
+    return [_numel(case[k]) for k in ("shape", "seq_shape", "in_shape", "mask_shape", "source_shape") if k in case] + [case.get("n", 0), case.get("num_bins", 0)]
+
+
+def classify_newer(lib, case) -> dict:
+    """What a case of the newer ops runs, by the library's pure functions on the description alone."""
+    t = fuzz.thresholds()
+    op, out = case["op"], {}
+    if op in fuzz.SELECT_OPS + fuzz.QUANTILE_OPS:
+        shape = case["shape"]
+        length = _numel(shape) if case["dim"] is None else shape[case["dim"] % len(shape)]
+        out["select"] = (selection_names[t.select_tier(length, case["dtype"])], length)
+        if op in fuzz.QUANTILE_OPS:
+            sides = 2 if case["interpolation"] in ("linear", "midpoint") else 1
+            out["quantile_path"] = "sort" if len(case["qs"]) * sides > capi.VRS_QUANTILE_MAX_TARGETS else "select"
+    elif op in fuzz.COUNT_OPS:
+        bins = case["num_bins"] if op == "bincount" else case["bins"]
+        if op == "bincount":
+            counter = 8 if case["weights"] not in (None, "float32") else 4
+        else:
+            counter = 8 if case.get("weight") and case["dtype"] == "float64" else 4
+        if bins and (_numel(case["shape"]) if op != "bincount" else case["n"]):
+            out["bincount"] = (counter, "global" if t.bincount_tier(bins, counter) == capi.VRS_BINCOUNT_GLOBAL else "lds", bins)
+        if op == "histogram" and _numel(case["shape"]):
+            n = _numel(case["shape"])
+            out["search"] = (_search_tier(lib, bins + 1, bins + 1, n, n, getattr(torch, case["dtype"])), bins + 1, n)
+    elif op == "segment_reduce":
+        out["reduce_levels"] = (t.reduce_levels_of(case["longest"]), case["longest"])
+    elif op in fuzz.REDUCE_OPS:
+        n, M = case["n"], case["M"]
+        out["form"] = (_form(lib, n, 4, True), n)
+        out["search"] = (_search_tier(lib, n, n, M + 1, M + 1, torch.int32), n, M + 1)
+    elif op in fuzz.SCAN_OPS:
+        shape = case["shape"]
+        if _numel(shape):
+            dim = case["dim"] % len(shape)
+            S, L, C = _numel(shape[:dim]), shape[dim], _numel(shape[dim + 1:])
+            src, dst = _scan_kernel_dtypes(case)
+            out["scan"] = (scan_mod.TIER_NAMES[t.scan_tier(S, L, C, src, dst, case["op"])], t.scan_levels_of(L), L)
+    else:
+        flags = _numel(case["mask_shape"] if "mask_shape" in case and case["op"] in ("mask_index", "mask_index_put") else
+                       [max(a, b) for a, b in zip(case["shape"], case["mask_shape"])] if "mask_shape" in case else case["shape"])
+        out["compact"] = (-(-flags // t.compact_tile), flags)
+    return out
+
+
+selection_names = importlib.import_module("vkradixsort_amd.selection").TIER_NAMES
+
+
+@pytest.fixture(scope="module")
+def newer_classes(lib, newer_cases):
+    return [classify_newer(lib, c) if c["op"] in fuzz.NEWER_OPS else classify(lib, c) for c in newer_cases]
+
+
+def test_the_newer_deck_is_deterministic_and_plain_and_leaves_the_first_alone():
+    import json
+    for seed, count in fuzz.COMMITTED_RUNS_NEWER:
+        a, b = list(fuzz.cases(seed, count, deck="newer")), list(fuzz.cases(seed, count, deck="newer"))
+        assert a == b and len(a) == count and [c["index"] for c in a] == list(range(count))
+        assert json.loads(json.dumps(a)) == a
+        assert a[:40] != list(fuzz.cases(seed + 1000, 40, deck="newer"))
+    assert len(fuzz.COMMITTED_RUNS_NEWER) == 1 and fuzz.COMMITTED_RUNS_NEWER[0][1] == 256
+    assert list(fuzz.cases(104, 32)) == list(fuzz.cases(104, 32, deck="first"))
+    with pytest.raises(ValueError):
+        fuzz.cases(1, 1, deck="both")
+
+
+def test_every_newer_op_and_dtype_the_wrappers_accept_occurs(newer_cases):
+    accepted = accepted_dtypes()
+    assert set(fuzz.NEWER_OPS) == {"kthvalue", "median", "nanmedian", "quantile", "nanquantile", "bincount", "histc", "histogram", "segment_reduce",
+                                   "index_add", "index_reduce", "scatter_reduce", "cumsum", "cumprod", "cummax", "cummin", "nonzero", "argwhere",
+                                   "count_nonzero", "masked_select", "masked_scatter", "mask_index", "mask_index_put"}
+    for op in fuzz.SCAN_OPS:  # (the scans refuse a dtype before the device too)
+        assert not _wrapper_takes(op, "complex64"), op
+    assert not _wrapper_takes("cummax", "uint16") and not _wrapper_takes("cummin", "uint16") and _wrapper_takes("cumsum", "uint16")
+    seen = {(c["op"], c["dtype"]) for c in newer_cases}
+    missing = {(op, dt) for op in fuzz.NEWER_OPS for dt in accepted[op]} - seen
+    assert not missing, sorted(missing)
+
+
+def test_every_newer_tier_occurs(newer_cases, newer_classes):
+    assert {c["select"][0] for c in newer_classes if "select" in c} == {"lds", "block", "grid"}
+    for ops in (fuzz.SELECT_OPS, fuzz.QUANTILE_OPS):
+        assert {k["select"][0] for c, k in zip(newer_cases, newer_classes) if c["op"] in ops} == {"lds", "block", "grid"}, ops
+    assert {c["quantile_path"] for c in newer_classes if "quantile_path" in c} == {"select", "sort"}
+    assert {c["bincount"][:2] for c in newer_classes if "bincount" in c} == {(w, t) for w in (4, 8) for t in ("lds", "global")}
+    assert {c["reduce_levels"][0] for c in newer_classes if "reduce_levels" in c} == {1, 2, 3}
+    assert {c["scan"][0] for c in newer_classes if "scan" in c} == {"tile", "three_launch", "single_pass"}
+    assert {c["scan"][1] for c in newer_classes if "scan" in c} >= {0, 1}
+    searches = [k["search"][0] for c, k in zip(newer_cases, newer_classes) if "search" in k and c["op"] in fuzz.REDUCE_OPS]
+    assert set(searches) == {"lds", "direct", "indexed"}, set(searches)
+    assert len({k["search"][0] for c, k in zip(newer_cases, newer_classes) if c["op"] == "histogram" and "search" in k}) >= 2  # (bucketize over the edges)
+    assert {c["compact"][0] for c in newer_classes if "compact" in c} >= {1, 2, 3, 5, 6}
+
+
+def test_every_newer_threshold_has_its_three_edges(newer_cases, newer_classes):
+    t = fuzz.thresholds()
+
+    def edges(values, cut, what):
+        assert {cut - 1, cut, cut + 1} <= set(values), (what, cut, sorted(v for v in set(values) if abs(v - cut) < 3))
+
+    lengths = {}
+    for c, k in zip(newer_cases, newer_classes):
+        if "select" in k:
+            lengths.setdefault(c["dtype"], []).append(k["select"][1])
+    # the block tier begins where a row's ranks leave LDS, which the tier function decides from the rank's width alone: 4-byte ranks for
+    # the seven dtypes of up to 4 bytes, 8-byte ranks for int64 and float64.  Three edges for each width's cut.
+    widths = {}
+    for d in fuzz.DTYPES:
+        widths.setdefault(t.select[d][0], []).append(d)
+    assert sorted(len(v) for v in widths.values()) == [2, 7] and sorted(widths[min(widths)]) == ["float64", "int64"]
+    for cut, names in widths.items():
+        edges([v for d in names for v in lengths.get(d, [])], cut, f"select block tier, {names}")
+    assert len({t.select[d][1] for d in fuzz.DTYPES}) == 1
+    edges([v for vs in lengths.values() for v in vs], t.select["float32"][1], "select grid tier")  # (the large minority)
+    for counter in (4, 8):
+        edges([k["bincount"][2] for k in newer_classes if "bincount" in k and k["bincount"][0] == counter], t.bincount[counter],
+              f"bincount LDS tier, {counter}-byte counters")
+    # histogram's bucketize over its bins + 1 edges: where that sequence leaves the search's LDS tier (float32's cut; float64's edge
+    # tensors are drawn around theirs too, two cases a round)
+    edges([k["search"][1] for c, k in zip(newer_cases, newer_classes) if c["op"] == "histogram" and c["dtype"] == "float32" and "search" in k],
+          t.search["float32"][0], "histogram: the edges leave LDS")
+    edges([k["reduce_levels"][1] for k in newer_classes if "reduce_levels" in k], t.reduce_levels[0], "two reduce levels")
+    edges([k["reduce_levels"][1] for k in newer_classes if "reduce_levels" in k], t.reduce_levels[1], "three reduce levels")
+    scans = [k["scan"][2] for k in newer_classes if "scan" in k]
+    assert t.scan_cuts("float32", "float32", "cumsum")[0] == t.scan_levels[0]  # (one tile: where the three-launch tier and the first level begin)
+    edges(scans, t.scan_levels[0], "scan tile")
+    single = t.scan_cuts("float32", "float32", "cumsum")[1]
+    assert single == t.scan_cuts("int32", "int32", "cumsum")[1] and single is not None
+    edges(scans, single, "scan single pass")
+    contributions = [c["n"] for c in newer_cases if c["op"] in fuzz.REDUCE_OPS and c["op"] != "segment_reduce"]
+    for cut in t.form_cuts[4, 1]:
+        edges(contributions, cut, "pair sort form")
+    edges(contributions, t.search["int32"][0], "sorted indices leave LDS")
+    edges([c["M"] + 1 for c in newer_cases if "M" in c], t.search["int32"][2], "destinations: the search index minimum")
+    flags = [k["compact"][1] for k in newer_classes if "compact" in k]
+    for tiles in (1, 2, 5):
+        edges(flags, tiles * t.compact_tile, "compaction tiles")
+    sizes = [v for c in newer_cases for v in _sizes(c)]
+    assert max(sizes) == fuzz.LARGE_ELEMENTS and 0 in sizes
+    small = sum(1 for c in newer_cases if max(_sizes(c)) <= fuzz.SMALL_ELEMENTS)
+    assert small >= 0.7 * len(newer_cases)
+
+
+def test_every_newer_class_of_argument_occurs(newer_cases):
+    by_op = {}
+    for c in newer_cases:
+        by_op.setdefault(c["op"], []).append(c)
+    newer = [c for c in newer_cases if c["op"] in fuzz.NEWER_OPS]
+    assert {c["k_class"] for c in by_op["kthvalue"]} == set(fuzz.K_CLASSES)
+    for c in by_op["kthvalue"]:
+        L = c["shape"][c["dim"] % len(c["shape"])]
+        assert c["k"] == max(1, min({"one": 1, "two": 2, "middle": (L + 1) // 2, "all_but_one": L - 1, "all": L}[c["k_class"]], L))
+    select = [c for c in newer if c["op"] in fuzz.SELECT_OPS + fuzz.QUANTILE_OPS]
+    assert {c["dim"] is None for c in select if c["op"] != "kthvalue"} == {False, True}
+    assert any(c["dim"] is not None and c["dim"] < 0 for c in select) and any(c["dim"] == 0 and len(c["shape"]) > 1 for c in select)
+    assert {c["keepdim"] for c in select} == {False, True}
+    for ops in (("median", "nanmedian"), fuzz.QUANTILE_OPS):
+        assert {c["nans"] for c in select if c["op"] in ops} == set(fuzz.NAN_KINDS), ops
+    quant = [c for c in newer if c["op"] in fuzz.QUANTILE_OPS]
+    assert {c["q_kind"] for c in quant} == set(fuzz.Q_KINDS) and {len(c["qs"]) for c in quant} == {1, 8, 9, 17}
+    assert {c["interpolation"] for c in quant} == set(fuzz.INTERPOLATIONS)
+    assert all(0.0 <= q <= 1.0 and float(torch.tensor(q, dtype=torch.float32)) == q for c in quant for q in c["qs"])
+    assert {c["weights"] for c in by_op["bincount"]} == set(fuzz.BINCOUNT_WEIGHTS)
+    assert any(0 < c["minlength"] < c["bins"] for c in by_op["bincount"]) and any(c["minlength"] > c["bins"] for c in by_op["bincount"])
+    assert {c["range"] for c in by_op["histc"]} == {"explicit", "data", "constant"} and {c["value_class"] for c in by_op["histc"]} == {"exact", "general"}
+    assert {(c["bins_kind"]) for c in by_op["histogram"]} == {"int", "int_range", "edges"} and {c["weight"] for c in by_op["histogram"]} == {False, True}
+    seg = by_op["segment_reduce"]
+    assert {c["reduce"] for c in seg} == {"sum", "mean", "max", "min", "prod"} and {c["initial"] for c in seg} == {None, 2}
+    assert {c["bounds"] for c in seg} == {"lengths", "offsets"}
+    assert any(0 in fuzz.segment_lengths(c["num_segments"], c["longest"], c["lengths_seed"]) for c in seg)
+    assert {c["reduce"] for c in by_op["index_reduce"]} == {"prod", "mean", "amax", "amin"}
+    assert {c["reduce"] for c in by_op["scatter_reduce"]} == {"sum", "prod", "mean", "amax", "amin"}
+    index_forms = by_op["index_add"] + by_op["index_reduce"] + by_op["scatter_reduce"]
+    assert {c["include_self"] for c in index_forms} == {False, True} and {c["alpha"] for c in by_op["index_add"]} == {1, 2}
+    assert {c["destinations"] for c in index_forms} == set(fuzz.DESTINATIONS) and {c["index_dtype"] for c in index_forms} == {"int32", "int64"}
+    assert {c["value_class"] for c in newer if "value_class" in c} == {"exact", "general", "wrap", "any", "count"}
+    for op in ("segment_reduce", "index_add", "index_reduce", "scatter_reduce", "cumsum", "cumprod", "histogram", "bincount"):
+        assert {"exact", "general"} <= {c["value_class"] for c in by_op[op]}, op
+    for op in ("index_add", "index_reduce", "scatter_reduce"):  # the bound over several contributions to one destination
+        assert any(c["value_class"] == "general" and c["destinations"] != "distinct" and c["n"] > 1 for c in by_op[op]), op
+    assert any(c["value_class"] == "general" and c["longest"] > 1 for c in seg)
+    assert sum(1 for c in by_op["bincount"] if c["weights"] is None and c["n"]) >= 2
+    assert sum(1 for c in by_op["histogram"] if not c["weight"] and _numel(c["shape"])) >= 2
+    scans = by_op["cumsum"] + by_op["cumprod"]
+    assert any(c["out_dtype"] is not None and c["out_dtype"] != c["dtype"] for c in scans) and any(c["out_dtype"] is None for c in scans)
+    masked = [c for c in newer if "mask_class" in c]
+    assert {c["mask_class"] for c in masked} == set(fuzz.MASK_CLASSES)
+    assert {c["broadcast"] for c in by_op["masked_select"] + by_op["masked_scatter"]} == {"same", "mask", "x"}
+    rows = by_op["mask_index"] + by_op["mask_index_put"]
+    assert {c["row_width"] for c in rows} == set(fuzz.ROW_WIDTHS) and {len(c["mask_shape"]) for c in rows} == {1, 2}
+    assert {c["values"] for c in by_op["mask_index_put"]} == {"exact", "broadcast", "scalar"}
+    assert {c["as_tuple"] for c in by_op["nonzero"]} == {False, True}
+    layouts = {k for c in newer for k in _newer_layouts(c)}
+    assert layouts == set(fuzz.LAYOUTS)
+    assert any(fuzz.DTYPE_BYTES[c["dtype"]] <= 2 and c["layout"]["kind"] == "offset" for c in newer)  # 1 to 3 bytes into a word: what aligned() is for
+    assert {c["stream"] for c in newer_cases} == {"current", "second"}
+    assert all((c["stream"] == "second") == (c["window"] % 5 == 4) for c in newer_cases)
+
+
+def _newer_layouts(case):
+    return [case[k]["kind"] for k in ("layout", "mask_layout", "source_layout", "index_layout", "w_layout") if k in case]
+
+
+def test_the_large_minority_and_both_pair_sort_kinds_occur(lib, newer_cases):
+    t = fuzz.thresholds()
+    large = [c for c in newer_cases if c["role"].startswith("large:")]
+    assert [c["index"] for c in large] == [i for i in range(len(newer_cases)) if i % fuzz.LARGE_EVERY == fuzz.LARGE_AT]
+    assert {c["role"].split(":")[1] for c in large} == set(fuzz.LARGE_KINDS_NEWER)
+    # Key + payload pairs take the pool form only above LARGE_ELEMENTS with the default tunings (the first deck's test says the same of
+    # its twins), and nothing here goes above that cap: the two kinds are drawn from the bare keys' pool minimum on, where the pair sort
+    # behind index_add is the counted form's deferred sort.  If pairs reach the pool form within the cap, the generator draws them there.
+    # (bisected up to a count where pairs are in the pool form, as tests/test_gpu_ops_fuzz.py's scenario finds it)
+    assert _form(lib, 1 << 27, 4, True) == "pool" and _form(lib, 1, 4, True) != "pool"
+    pairs_pool = fuzz._first(lambda v: _form(lib, v, 4, True) == "pool", 1, 1 << 27)
+    assert _form(lib, pairs_pool, 4, True) == "pool" and _form(lib, pairs_pool - 1, 4, True) != "pool"
+    assert pairs_pool > fuzz.LARGE_ELEMENTS and t.pool_min_pairs is None, "pairs reach the pool form within LARGE_ELEMENTS now: the two kinds move there"
+    assert all(_form(lib, n, 4, True) != "pool" for n in t.form_cuts[4, True] + [fuzz.LARGE_ELEMENTS, fuzz.LARGE_ELEMENTS - 1])
+    pool_min = t.pool_min_pairs or t.pool_min
+    skewed = [c for c in large if c["role"] == "large:index_add_skewed"]
+    assert skewed and all(c["op"] == "index_add" and c["M"] <= 50 and pool_min < c["n"] <= fuzz.LARGE_ELEMENTS for c in skewed)
+    edge = [c for c in large if c["role"] == "large:index_add_pool_edge"]
+    assert {c["n"] - pool_min for c in edge} <= {-1, 0, 1} and len({c["n"] for c in edge}) >= 2
+    assert all(c["destinations"] == "distinct" and c["M"] >= c["n"] for c in edge)
+    assert {c["shape"][-1] for c in large if c["role"] in ("large:masked_select_large", "large:nonzero_large")} == {fuzz.LARGE_ELEMENTS}
+    assert all(c["num_bins"] >= 1 << 20 for c in large if c["role"] == "large:bincount_global")
+
+
+def test_every_window_has_its_neighbour_and_a_sort_is_pending_before_a_newer_op(lib, newer_cases):
+    windows = {}
+    for c in newer_cases:
+        windows.setdefault(c["window"], []).append(c)
+    pending_windows = 0
+    for w, group in windows.items():
+        assert len(group) == 4
+        old = [c for c in group if c["op"] in fuzz.FIRST_OPS]
+        assert old, w
+        first = group[0]
+        if first["role"] == "pending_sort":
+            assert first["op"] in ("sort", "sort_values", "unique") and len(first["shape"]) == 1 and first["shape"][0] >= capi.ONE_CALL_MIN_KEYS_DEFAULT
+            assert "form" in classify(lib, first)  # (a one-call sort)
+            assert any(c["op"] in fuzz.NEWER_OPS for c in group[1:])
+            pending_windows += 1
+    assert all(sum(1 for v in range(w0, w0 + 8) if windows[v][0]["role"] == "pending_sort") >= 1 for w0 in range(0, len(windows) - 7))
+    assert pending_windows * 2 >= len(windows)  # every second neighbour
+
+
+def test_no_newer_case_leaves_an_ops_documented_domain(newer_cases):
+    accepted = accepted_dtypes()
+    for c in newer_cases:
+        op = c["op"]
+        assert c["dtype"] in accepted[op], c
+        assert max(_sizes(c)) <= fuzz.LARGE_ELEMENTS, c
+        if op not in fuzz.NEWER_OPS:
+            continue
+        cls = c.get("value_class")
+        if op in fuzz.SELECT_OPS + fuzz.QUANTILE_OPS:
+            nd = len(c["shape"])
+            assert nd >= 1 and _numel(c["shape"]) > 0 and (c["dim"] is None or -nd <= c["dim"] < nd), c
+        if op == "bincount":
+            assert c["bins"] - 1 <= {"uint8": 255, "int8": 127, "int16": 32767}.get(c["dtype"], 1 << 62) and c["minlength"] >= 0, c
+        if op in ("histc", "histogram"):
+            assert c["bins"] >= 1 and (op == "histogram" or c["lo"] <= c["hi"]), c
+        if op == "segment_reduce":
+            lengths = fuzz.segment_lengths(c["num_segments"], c["longest"], c["lengths_seed"])
+            assert lengths.sum() == c["shape"][0] and lengths.max() == c["longest"] and lengths.min() >= 0, c
+            terms, start, per_term = c["longest"], 2, 1
+        if op in ("index_add", "index_reduce", "scatter_reduce"):
+            assert c["shape"][c["dim"]] == c["M"] and c["source_shape"][c["dim"]] >= c["n"] and (c["destinations"] != "distinct" or c["M"] >= c["n"]), c
+            assert op != "scatter_reduce" or len(c["shape"]) == 1, c
+            terms, start, per_term = 1 if c["destinations"] == "distinct" else c["n"], 4, 2
+        if op in ("cumsum", "cumprod") and _numel(c["shape"]):
+            terms, start, per_term = c["shape"][c["dim"] % len(c["shape"])], 0, 1
+        if op in fuzz.REDUCE_OPS + ("cumsum", "cumprod") and cls in ("exact", "general") and _numel(c["shape"]):
+            out = (c.get("out_dtype") or c["dtype"]) if op in ("cumsum", "cumprod") else c["dtype"]
+            if cls == "general":  # the condition of the bound: t * u < 0.1, the input or initial counted as a term
+                assert (terms + 1) * fuzz.EPS[out] < 0.1, c
+            elif c.get("reduce", "sum") != "prod" and op != "cumprod":  # every partial sum, in any order, is an integer the dtype holds
+                assert start + terms * per_term <= fuzz.EXACT_LIMIT[out], c
+        if op in ("mask_index", "mask_index_put"):
+            assert c["shape"][:len(c["mask_shape"])] == c["mask_shape"], c
+
+
+# ---- torch's own functions through check(): the references and their bounds are right ---------------------------------------------
+
+class _Torch:
+    """torch's CPU functions under the library's names and calling conventions."""
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+    index_add = staticmethod(lambda x, d, i, s, alpha=1: torch.index_add(x, d, i.long(), s, alpha=alpha))
+    index_reduce = staticmethod(lambda x, d, i, s, r, include_self=True: torch.index_reduce(x, d, i.long(), s, r, include_self=include_self))
+    scatter_reduce = staticmethod(lambda x, d, i, s, r, include_self=True: torch.scatter_reduce(x, d, i.long(), s[:i.numel()], r, include_self=include_self))
+    mask_index = staticmethod(lambda x, m: x[m])
+    mask_index_put = staticmethod(lambda x, m, v: torch.index_put(x, (m,), v))
+    masked_scatter = staticmethod(lambda x, m, s: torch.broadcast_tensors(x, m)[0].contiguous().masked_scatter(m, s))
+
+    @staticmethod
+    def histc(x, bins, min, max):
+        """(float16 / bfloat16: torch sums float ones in the dtype and stops growing; its float32 counts of the same values, which the
+        upcast keeps exactly, rounded to the dtype once as the op defines its counts)"""
+        if x.dtype in (torch.float16, torch.bfloat16):
+            return fuzz.as_count(torch.histc(x.float(), bins, min=min, max=max).long().numpy(), x.dtype)
+        return torch.histc(x, bins, min=min, max=max)
+
+    @staticmethod
+    def segment_reduce(x, reduce, lengths=None, offsets=None, initial=None):
+        kw = {"lengths": lengths.long()} if lengths is not None else {"offsets": offsets.long()}
+        return torch.segment_reduce(x, reduce, initial=initial, **kw)
+
+    @staticmethod
+    def histogram(x, bins, range=None, weight=None):
+        return torch.histogram(x, bins, weight=weight) if range is None else torch.histogram(x, bins, range=range, weight=weight)
+
+
+# where torch has no such function on the CPU or defines the answer differently: by name, not computed
+TORCH_SKIPS = {
+    "segment_reduce of int32 / int64": lambda c: c["op"] == "segment_reduce" and c["dtype"] in ("int32", "int64"),                # torch has none
+    "bincount of an empty input with weights": lambda c: c["op"] == "bincount" and c["n"] == 0 and c["weights"] is not None,      # torch: int64
+    "histc outside the exact class": lambda c: c["op"] == "histc" and c["value_class"] != "exact",                                # another formula on the CPU
+}
+THROUGH_TORCH_ELEMENTS = fuzz.SMALL_ELEMENTS
+
+
+def test_torchs_own_cpu_functions_pass_the_fuzzs_checks(newer_cases):
+    """Every newer-op case of the committed run below SMALL_ELEMENTS: its inputs built on the CPU, the corresponding torch function run
+    on them (on contiguous copies: this is about the references, and torch.median reads an expanded view wrongly), and torch's result
+    handed to check() as if it were the library's.  It reports nothing: the references agree with torch bit for bit where they claim
+    bits, and torch's own rounding stays within the bounds where they claim bounds."""
+    ran = {}
+    for c in newer_cases:
+        if c["op"] not in fuzz.NEWER_OPS or max(_sizes(c)) > THROUGH_TORCH_ELEMENTS:
+            continue
+        if any(applies(c) for applies in TORCH_SKIPS.values()):
+            continue
+        cpu, _ = fuzz.prepare(c, None)
+        result = fuzz.call_newer(_Torch(), c, {k: v.contiguous() for k, v in cpu.items()})
+        assert fuzz.check(c, cpu, result) == [], c
+        ran[c["op"]] = ran.get(c["op"], 0) + 1
+    assert set(ran) == set(fuzz.NEWER_OPS), sorted(set(fuzz.NEWER_OPS) - set(ran))
+
+
+# ---- one changed element: the references would notice ------------------------------------------------------------------------------
+
+def _ulp_step(t, flat):
+    """t with element `flat` moved to the next representable value (floats) or changed by one (integers, bool flipped)."""
+    out = t.clone().reshape(-1)
+    if t.dtype == torch.bool:
+        out[flat] = ~out[flat]
+    elif t.dtype.is_floating_point:
+        bits = out.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+        bits[flat] += 1 if out[flat] >= 0 else -1  # (away from zero; of a finite value)
+    else:
+        out[flat] += 1
+    return out.reshape(t.shape)
+
+
+def _beyond(want, bound, flat, dtype):
+    """The reference `want` (float64) as the dtype, element `flat` moved just beyond its bound."""
+    out = want.to(dtype).reshape(-1).clone()
+    target = want.reshape(-1)[flat] + 1.05 * bound.reshape(-1)[flat] + torch.finfo(dtype).tiny
+    out[flat] = target.to(dtype)
+    while (out[flat].double() - want.reshape(-1)[flat]).abs() <= bound.reshape(-1)[flat]:
+        out = _ulp_step(out, flat) if out[flat] > 0 else out.index_fill(0, torch.tensor([flat]), torch.finfo(dtype).tiny)
+    return out.reshape(want.shape)
+
+
+def _as_returned(wants):
+    return [w.want.to(w.dtype) if w.rule == "bound" else w.want for w in wants]
+
+
+def test_one_changed_element_is_reported_by_name(newer_cases):
+    """For one case per op (the first of the run below SMALL_ELEMENTS whose output has an element to change): the reference's own outputs
+    pass check(), and with one element changed -- the last, or one in the second tile where there is one; 1 ulp where the rule is exact,
+    just beyond the bound where it is a bound -- check() reports that output by its name."""
+    tile = fuzz.thresholds().compact_tile
+    seen, rules = {}, set()  # op -> the value classes done (a float sum or product: one case per class that occurs)
+    for c in newer_cases:
+        op, cls = c["op"], c.get("value_class")
+        if op not in fuzz.NEWER_OPS or max(_sizes(c)) > fuzz.SMALL_ELEMENTS:
+            continue
+        if cls in seen.get(op, ()) or (op in seen and cls not in ("exact", "general")):
+            continue
+        cpu, _ = fuzz.prepare(c, None)
+        wants = fuzz.reference_newer(c, cpu)
+        if any(w.want.numel() == 0 or (w.rule in ("value", "bits") and w.want.dtype.is_floating_point and not torch.isfinite(w.want.reshape(-1)[-1]))
+               for w in wants):
+            continue
+        outputs = _as_returned(wants)
+        assert fuzz.check(c, cpu, tuple(outputs)) == [], c
+        for which, w in enumerate(wants):
+            n = w.want.numel()
+            flat = tile + 1 if n > tile + 1 else n - 1
+            changed = list(outputs)
+            if w.rule == "index":  # (on a row without ties where there is one: a tie leaves the index open; else out of range)
+                free = torch.nonzero(w.free.reshape(-1))
+                changed[which] = outputs[which].clone()
+                if free.numel():
+                    changed[which].view(-1)[int(free[-1])] += 1
+                else:
+                    changed[which].view(-1)[flat] = w.rows.shape[w.dim]
+            elif w.rule == "bound":
+                if not torch.isfinite(w.want.reshape(-1)[flat]):
+                    continue
+                changed[which] = _beyond(w.want, w.bound, flat, w.dtype)
+            else:
+                changed[which] = _ulp_step(outputs[which], flat)
+            lines = fuzz.check(c, cpu, tuple(changed))
+            assert lines and any(line.startswith(w.name) for line in lines), (c, w.name, lines)
+            rules.add(w.rule)
+        seen.setdefault(op, set()).add(cls)
+    assert set(seen) == set(fuzz.NEWER_OPS), sorted(set(fuzz.NEWER_OPS) - set(seen))
+    assert {"exact", "general"} <= seen["cumsum"] | seen["cumprod"]
+    assert {"exact", "general"} <= seen["index_add"] | seen["index_reduce"] | seen["scatter_reduce"] | seen["segment_reduce"]
+    assert rules == {"bits", "value", "bound", "index"}
+
+
+def test_a_swapped_pair_of_tied_indices_and_a_dropped_row_are_reported(newer_cases):
+    x = torch.tensor([3, 5, 5, 1, 5], dtype=torch.int32)
+    case = {"op": "cummax", "dtype": "int32", "dim": 0}
+    values, indices = torch.cummax(x, 0)
+    assert fuzz.check(case, {"x": x}, (values, indices)) == []
+    swapped = indices.clone()
+    swapped[2], swapped[4] = indices[1], indices[2]  # (the earlier of two equal values: still a position of the maximum)
+    assert bool((x[swapped] == values).all())
+    lines = fuzz.check(case, {"x": x}, (values, swapped))
+    assert lines and lines[0].startswith("indices")
+    c = next(c for c in newer_cases if c["op"] == "mask_index" and c["mask_class"] in ("half", "all") and max(_sizes(c)) <= fuzz.SMALL_ELEMENTS)
+    cpu, _ = fuzz.prepare(c, None)
+    rows = cpu["x"][cpu["mask"]]
+    assert rows.shape[0] > 1 and fuzz.check(c, cpu, rows) == []
+    lines = fuzz.check(c, cpu, rows[:-1])
+    assert lines and lines[0].startswith("rows")

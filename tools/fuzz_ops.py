@@ -9,6 +9,17 @@ with references written on torch's CPU functions and numpy alone.  It stops at t
 case index, the last eight descriptions, the first differing position and a replay line, and starts nothing more on the GPU.
    python tools/fuzz_ops.py SECONDS SEED            (soak: the same runner with a time budget)
    python tools/fuzz_ops.py 0 SEED --count N        (replay the first N cases of a seed)
+Two decks of ops, never folded into one (`--deck`, `cases(..., deck=)`, `run(..., deck=)`).  "first": sort, sort_values, argsort, sort_rows,
+topk, unique, unique_consecutive, searchsorted, bucketize; its stream of descriptions is pinned by a hash in tests/test_ops_fuzz_cpu.py.
+"newer": the selections (kthvalue, median, nanmedian, quantile, nanquantile), the counts (bincount, histc, histogram), the reductions
+(segment_reduce, index_add, index_reduce, scatter_reduce), the scans (cumsum, cumprod, cummax, cummin) and the compactions (nonzero,
+argwhere, count_nonzero, masked_select, masked_scatter, mask_index, mask_index_put).  Every window of the newer deck holds a case of the
+first deck's ops, and every second window opens with a 1-D sort / sort_values / unique of the one-call minimum or more, so that a
+deferred sort is pending when the next op's settle_pending runs.  Its outputs are held to torch's CPU functions and numpy bit for bit
+wherever the result is defined exactly; float sums, products and means come in two value classes that the description names: "exact"
+(small integers, +-1 factors, lengths capped so that every partial result is representable: == against torch) and "general" (random
+finite values against the same operation in float64, within (t + 1) u sum|x| for a sum of t terms, t u / (1 - t u) relative for a
+product, one u more for a mean's division, u the dtype's epsilon, t u < 0.1 kept by the generator).
 tools/fuzz_gpu.py covers the raw key and pair sorts on a context of its own."""
 from __future__ import annotations
 
@@ -25,12 +36,21 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 DTYPES = ["int8", "uint8", "int16", "int32", "int64", "float16", "bfloat16", "float32", "float64"]
-DTYPE_BYTES = {"int8": 1, "uint8": 1, "int16": 2, "int32": 4, "int64": 8, "float16": 2, "bfloat16": 2, "float32": 4, "float64": 8}
+DTYPE_BYTES = {"bool": 1, "int8": 1, "uint8": 1, "int16": 2, "int32": 4, "int64": 8, "float16": 2, "bfloat16": 2, "float32": 4, "float64": 8}
 FLOATS = ("float16", "bfloat16", "float32", "float64")
 KEY32, KEY3264 = ["int32", "float32"], ["int32", "int64", "float32", "float64"]
 # what each wrapper accepts (tests/test_ops_fuzz_cpu.py reads the same lists out of the wrappers' refusals)
 OP_DTYPES = {"sort": DTYPES, "sort_values": DTYPES, "argsort": DTYPES, "sort_rows": KEY32, "topk": KEY32, "unique": KEY3264,
              "unique_consecutive": KEY3264, "searchsorted": DTYPES, "bucketize": DTYPES}
+FIRST_OPS = tuple(OP_DTYPES)  # the first deck's ops; the newer deck's follow
+TEN, SIX = ["bool"] + DTYPES, ["int32", "int64", "float16", "bfloat16", "float32", "float64"]
+INDEX_DTYPES = ["uint8", "int8", "int16", "int32", "int64"]
+OP_DTYPES.update({"kthvalue": DTYPES, "median": DTYPES, "nanmedian": DTYPES, "quantile": ["float32", "float64"], "nanquantile": ["float32", "float64"],
+                  "bincount": INDEX_DTYPES, "histc": list(FLOATS), "histogram": ["float32", "float64"],
+                  "segment_reduce": SIX, "index_add": SIX, "index_reduce": SIX, "scatter_reduce": SIX,
+                  "cumsum": TEN, "cumprod": TEN, "cummax": TEN, "cummin": TEN,
+                  "nonzero": TEN, "argwhere": TEN, "count_nonzero": TEN, "masked_select": TEN, "masked_scatter": TEN, "mask_index": TEN, "mask_index_put": TEN})
+NEWER_OPS = tuple(op for op in OP_DTYPES if op not in FIRST_OPS)
 OP_WEIGHT = {"searchsorted": 3, "bucketize": 2, "topk": 4, "sort_rows": 3, "unique": 2, "unique_consecutive": 2}  # (turns per round of the op x dtype deck: one unless named)
 CONTIGUOUS_ONLY = ("sort_rows", "topk", "unique", "unique_consecutive")  # these refuse a non-contiguous tensor
 LAYOUTS = ["contiguous", "transposed", "strided", "offset", "expanded"]
@@ -49,6 +69,7 @@ SECOND_STREAM_EVERY = 5      # every fifth window runs on a second stream
 PENDING_BYTES_CAP = 1 << 30
 # (seed, count) of the runs tests/test_gpu_ops_fuzz.py makes; tests/test_ops_fuzz_cpu.py holds them to what the generator claims to reach
 COMMITTED_RUNS = [(104, 256)]
+COMMITTED_RUNS_NEWER = [(491, 256)]  # the same for the newer deck
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -105,6 +126,58 @@ class Thresholds:
                 table = _first(lambda q: self.search_tier(out, out, q, q, code) == capi.VRS_SEARCH_TABLE, 0, top)
             index = _first(lambda q: self.search_tier(2 * out, out, 2 * q, q, code) == capi.VRS_SEARCH_INDEXED, 0, top)
             self.search[name] = (out, table, index)
+        # -- what the newer deck straddles
+        self.select = {}  # dtype -> [first block-tier row length, first grid-tier row length]
+        for name in DTYPES:
+            self.select[name] = [_first(lambda L, t=t: self.select_tier(L, name) >= t, 1, top) for t in (capi.VRS_SELECT_BLOCK, capi.VRS_SELECT_GRID)]
+        self.bincount = {cb: _first(lambda b: self.bincount_tier(b, cb) == capi.VRS_BINCOUNT_GLOBAL, 1, top) for cb in (4, 8)}  # counter bytes -> first global bins
+        self.reduce_levels = [_first(lambda L, k=k: self.reduce_levels_of(L) >= k, 1, top) for k in (2, 3)]
+        self.scan_levels = [_first(lambda L, k=k: self.scan_levels_of(L) >= k, 1, top) for k in (1, 2)]
+        self._scan_cuts = {}
+        # the first count up to the cap at which key + payload pairs take the pool form (None: only above the cap, or never): a walk over the
+        # form's changes up to the cap, as form_cuts is, so that a minimum that comes within the cap is found wherever it lies
+        pairs_pool = [n for n in self.form_cuts[4, 1] if self.sort_form(n, 4, 1) == "pool"]
+        self.pool_min_pairs = pairs_pool[0] if pairs_pool else None
+        self.compact_tile = capi.COMPACT_TILE_ELEMS_DEFAULT
+
+    def select_tier(self, length: int, dtype: str) -> int:
+        lo, hi, tier = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int()
+        assert self.lib.vrs_select_tier_for(0, length, length, getattr(self.capi, "VRS_SORT_" + dtype.upper()), self.capi.SELECT_GRID_MIN_KEYS_DEFAULT,
+                                            ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(tier)) == 0
+        return tier.value
+
+    def bincount_tier(self, bins: int, counter_bytes: int) -> int:
+        tier = ctypes.c_int()
+        assert self.lib.vrs_bin_count_tier_for(bins, counter_bytes, self.capi.BINCOUNT_LDS_BYTES_DEFAULT, ctypes.byref(tier)) == 0
+        return tier.value
+
+    def reduce_levels_of(self, length: int) -> int:
+        levels = ctypes.c_uint32()
+        assert self.lib.vrs_segment_reduce_levels_for(length, self.capi.REDUCE_CHUNK_ROWS_DEFAULT, ctypes.byref(levels)) == 0
+        return levels.value
+
+    def scan_levels_of(self, length: int) -> int:
+        levels = ctypes.c_uint32()
+        assert self.lib.vrs_scan_levels_for(length, self.capi.SCAN_TILE_ROWS_DEFAULT, ctypes.byref(levels)) == 0
+        return levels.value
+
+    def scan_tier(self, S: int, L: int, C: int, dtype: str, out_dtype: str, op: str) -> int:
+        c, tier = self.capi, ctypes.c_int()
+        code = lambda name: getattr(c, "VRS_SORT_" + name.upper())  # noqa: E731
+        assert self.lib.vrs_scan_tier_for(S, L, C, code(dtype), code(out_dtype), getattr(c, "VRS_SCAN_" + SCAN_KERNEL_OP[op]), c.SCAN_TILE_ROWS_DEFAULT,
+                                          c.SCAN_SINGLE_PASS_MIN_ROWS_DEFAULT, ctypes.byref(tier)) == 0
+        return tier.value
+
+    def scan_cuts(self, dtype: str, out_dtype: str, op: str):
+        """[first three-launch length, first single-pass length or None] of one segment of one column of this kernel dtype pair and op."""
+        key = (dtype, out_dtype, op)
+        if key not in self._scan_cuts:
+            top, cuts = LARGE_ELEMENTS * 4, []
+            for tier in (self.capi.VRS_SCAN_THREE_LAUNCH, self.capi.VRS_SCAN_SINGLE_PASS):
+                reached = self.scan_tier(1, top, 1, dtype, out_dtype, op) >= tier
+                cuts.append(_first(lambda L: self.scan_tier(1, L, 1, dtype, out_dtype, op) >= tier, 1, top) if reached else None)
+            self._scan_cuts[key] = cuts
+        return self._scan_cuts[key]
 
     def segment_tier(self, length: int, wide: bool, pairs: bool) -> int:
         fn = self.lib.vrs_segment_tier_for_u64 if wide else self.lib.vrs_segment_tier_for
@@ -179,7 +252,7 @@ class _Gen:
         self.t = thresholds()
         self.rng = rng = np.random.Generator(np.random.PCG64(seed))
         self.count, self.window = count, window
-        pairs = [(op, dt) for op, dts in OP_DTYPES.items() for dt in dts for _ in range(OP_WEIGHT.get(op, 1))]
+        pairs = [(op, dt) for op in FIRST_OPS for dt in OP_DTYPES[op] for _ in range(OP_WEIGHT.get(op, 1))]
         self.op_dtype = _Deck(rng, pairs)
         self.layout = _Deck(rng, LAYOUTS)
         self.layout_contiguous = _Deck(rng, ["contiguous", "offset"])
@@ -473,9 +546,13 @@ class _Gen:
                 self._index += 1
 
 
-def cases(seed: int, count: int, window: int = 4):
-    """`count` case descriptions of `seed`: plain dicts of numbers, strings and lists.  The same everywhere; needs no device."""
-    return iter(_Gen(seed, count, window))
+def cases(seed: int, count: int, window: int = 4, deck: str = "first"):
+    """`count` case descriptions of `seed`: plain dicts of numbers, strings and lists.  The same everywhere; needs no device.
+    deck "first": sort, topk, unique and the searches; "newer": the selections, counts, reductions, scans and compactions, every window with
+    a neighbour from the first deck's ops."""
+    if deck not in ("first", "newer"):
+        raise ValueError(f"unknown deck {deck!r}")
+    return iter((_Gen if deck == "first" else _GenNewer)(seed, count, window))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -694,6 +771,1027 @@ def ref_searchsorted(seq, values, right: bool, out_int32: bool, sorter=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# the newer deck: its generator
+
+SCAN_KERNEL_OP = {"cumsum": "SUM", "cumprod": "PROD", "cummax": "MAX", "cummin": "MIN"}
+SELECT_OPS, QUANTILE_OPS, COUNT_OPS = ("kthvalue", "median", "nanmedian"), ("quantile", "nanquantile"), ("bincount", "histc", "histogram")
+REDUCE_OPS, SCAN_OPS = ("segment_reduce", "index_add", "index_reduce", "scatter_reduce"), tuple(SCAN_KERNEL_OP)
+COMPACT_OPS = ("nonzero", "argwhere", "count_nonzero", "masked_select", "masked_scatter", "mask_index", "mask_index_put")
+K_CLASSES = ["one", "two", "middle", "all_but_one", "all"]
+Q_KINDS = ["float", "0d", "t1", "t8", "t9", "t17"]  # a Python float, a 0-d tensor, a tensor of so many values
+INTERPOLATIONS = ["linear", "lower", "higher", "midpoint", "nearest"]
+NAN_KINDS = ["none", "some", "row"]                 # no NaN put in, NaNs in some rows, and one row of NaNs alone besides
+DESTINATIONS = ["equal", "distinct", "zipf"]
+MASK_CLASSES = ["none", "all", "sparse", "half", "one_tile"]
+ROW_WIDTHS = [1, 3, 4, 1025]
+BINCOUNT_WEIGHTS = [None, "float32", "float64", "int32", "float16"]  # (the last two: "another dtype", which the wrapper .double()s)
+SCAN_TARGETS = {"bool": [None, "int32", "float32"], "int8": [None, "int32", "int64", "float32"], "uint8": [None, "int32", "float64"],
+                "int16": [None, "int32", "float32"], "int32": [None, "int32", "int64", "float64"], "int64": [None, "float64"],
+                "float16": [None, "float32"], "bfloat16": [None, "float32", "float64"], "float32": [None, "float64"], "float64": [None]}
+# turns per round beyond one: the (op, dtype) pairs that alone can draw the edges of a cut (a bincount whose dtype reaches the cut, the
+# histogram whose edge tensor straddles the search's LDS cut)
+PAIR_WEIGHT_NEWER = {("bincount", "int32"): 3, ("bincount", "int64"): 2, ("histogram", "float32"): 3, ("quantile", "float32"): 2}  # (and six kinds of q, five interpolations for four pairs)
+LARGE_KINDS_NEWER = ["index_add_skewed", "index_add_pool_edge", "cumsum_single_pass", "reduce_three_levels", "kthvalue_grid", "quantile_grid",
+                     "bincount_global", "masked_select_large", "nonzero_large"]
+EPS = {"float16": 2.0 ** -10, "bfloat16": 2.0 ** -7, "float32": 2.0 ** -23, "float64": 2.0 ** -52}  # u of the bounds: the dtype's epsilon
+EXACT_LIMIT = {"float16": 2048, "bfloat16": 256, "float32": 1 << 24, "float64": 1 << 53}  # every integer up to here is held
+
+
+def terms_cap(dtype: str, value_class: str, per_term: int = 1, start: int = 0) -> int:
+    """The most terms a float sum or product of this class may have.  exact: terms of at most `per_term` on top of `start` stay within
+    the integers the dtype holds, in any order.  general: t * u < 0.1, the condition of the bound (one term kept for an input or initial)."""
+    if dtype not in FLOATS:
+        return 1 << 40
+    if value_class == "exact":
+        return (EXACT_LIMIT[dtype] - start) // per_term
+    return int(0.1 / EPS[dtype]) - 2
+
+
+def segment_lengths(num_segments: int, longest: int, seed: int):
+    """The lengths of a segment_reduce case: one segment of `longest` rows among short ones, about one in five of them empty."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lengths = rng.integers(1, min(longest, 64) + 1, size=num_segments)
+    lengths[rng.random(num_segments) < 0.2] = 0
+    lengths[int(rng.integers(num_segments))] = longest
+    return lengths.astype(np.int64)
+
+
+class _GenNewer(_Gen):
+    """The newer deck.  Window w of four holds: w even, a 1-D sort / sort_values / unique of the one-call minimum or more first (a deferred
+    sort is pending when the next op's settle_pending runs); w odd, a case of the first deck's ops last; case i with i % LARGE_EVERY ==
+    LARGE_AT is of the large minority; every other case is the next (op, dtype) of the newer ops' deck."""
+
+    def __init__(self, seed: int, count: int, window: int):
+        super().__init__(seed, count, window)
+        if window < 4:
+            raise ValueError("the newer deck takes windows of four cases or more")
+        rng = self.rng
+        self.new_op_dtype = _Deck(rng, [(op, dt) for op in NEWER_OPS for dt in OP_DTYPES[op] for _ in range(PAIR_WEIGHT_NEWER.get((op, dt), 1))])
+        self.pending = _Deck(rng, [(op, dt) for op in ("sort", "sort_values", "unique") for dt in OP_DTYPES[op]])
+        self.large_newer = _Deck(rng, LARGE_KINDS_NEWER)
+        self.named, self.turns = {}, {}
+
+    def _pick(self, name: str, items):
+        """The next item of the deck `name` (made of `items` at its first use)."""
+        if name not in self.named:
+            self.named[name] = _Deck(self.rng, items)
+        return self.named[name].draw()
+
+    def _turn(self, name: str, items):
+        """The items of `name` in their order, round and round: for the ops with so few cases a round that the order has to be planned."""
+        self.turns[name] = self.turns.get(name, -1) + 1
+        return items[self.turns[name] % len(items)]
+
+    def _preferred(self, op: str, first, then=None) -> str:
+        """A dtype for a large case of `op`: the deck's next one of `first` while the round still holds one, else its next one of `then`;
+        when the round holds neither, any of them, and the deck keeps its turn (the case adds no pair to the round then)."""
+        for allowed in (first, then or ()):
+            if any(p[0] == op and p[1] in allowed for p in self.new_op_dtype.left):
+                return self.new_op_dtype.draw(lambda p: p[0] == op and p[1] in allowed)[1]
+        allowed = tuple(first) + tuple(then or ())
+        return allowed[int(self.rng.integers(len(allowed)))]
+
+    def _done(self, case: dict, role: str = "newer") -> list:
+        case.update(deck="newer", role=role, data_seed=self._seed())
+        return [case]
+
+    def _value_dist(self, dtype: str) -> str:
+        return "uniform" if dtype == "bool" else self._dist(dtype)
+
+    def _rows_shape(self, length: int, cap: int = SMALL_ELEMENTS):
+        shape, dim = self._shape_with(self._rows_for(length, cap), length)
+        return shape, (dim - len(shape) if self.rng.integers(2) else dim)
+
+    def _short_or(self, name: str, cuts, cap: int) -> int:
+        """A length for `name`: 1 to 3, 2 to 64, or (three times in four) one of the class built on `cuts`."""
+        kind = int(self.rng.integers(8))
+        if kind == 0:
+            return int(self.rng.integers(1, 4))
+        if kind == 1:
+            return int(self.rng.integers(2, 65))
+        return _around(self, cuts, cap)
+
+    # -- the neighbours from the first deck -------------------------------------------------------------------------------------
+    def _pending_sort(self) -> list:
+        rng = self.rng
+        op, dtype = self.pending.draw()
+        low = self.t.capi.ONE_CALL_MIN_KEYS_DEFAULT
+        n = int(rng.integers(low, SMALL_ELEMENTS + 1)) if rng.integers(4) else low + int(rng.integers(2))
+        if op == "unique":
+            case = self._unique("unique", dtype, n=n)
+            case["shape"], case["layout"] = [n], self._layout([n], True)
+        else:
+            case = {"op": op, "dtype": dtype, "shape": [n], "dim": 0, "descending": bool(rng.integers(2)), "layout": self._layout([n]),
+                    "dist": self._dist(dtype), "data_seed": self._seed()}
+        case.update(deck="newer", role="pending_sort")
+        return [case]
+
+    def _neighbour(self) -> list:
+        op, dtype = self.op_dtype.draw()
+        if op in ("sort", "sort_values", "argsort"):
+            case = self._sort(op, dtype)
+        elif op == "sort_rows":
+            case = self._sort_rows(dtype)
+        elif op == "topk":
+            case = self._topk(dtype)
+        elif op in ("unique", "unique_consecutive"):
+            case = self._unique(op, dtype)
+        else:
+            case = self._search(op, dtype, variant=self.variant.draw(lambda v: v != "dependent"))[0]
+        case.update(deck="newer", role="neighbour")
+        return [case]
+
+    # -- selection --------------------------------------------------------------------------------------------------------------
+    def _select_length(self, dtype: str, family: str = "select") -> int:
+        """A row length: the block tier's cut for this dtype's rank width - 1, + 0, + 1, each once in four draws of that width, else short
+        or anywhere up to half the small cap."""
+        cut = self.t.select[dtype][0]
+        step = self._pick(f"{family}_length_{cut}", [-1, 0, 1, None])
+        if step is not None:
+            return cut + step
+        return int(self.rng.integers(1, 200)) if self.rng.integers(2) else int(self.rng.integers(200, SMALL_ELEMENTS // 2))
+
+    def _select(self, op: str, dtype: str, length=None) -> dict:
+        rng = self.rng
+        if length is None:
+            length = self._select_length(dtype)
+            shape, dim = self._rows_shape(length)
+        else:
+            shape, dim = ([length], 0) if rng.integers(2) else ([2, length], -1)
+        case = {"op": op, "dtype": dtype, "shape": shape, "dim": dim, "keepdim": self._pick("keepdim", [False, True]), "layout": self._layout(shape),
+                "dist": self._dist(dtype), "nans": self._pick("nans_" + op, NAN_KINDS) if dtype in FLOATS else "none"}
+        if op == "kthvalue":
+            which = self._pick("k", K_CLASSES)
+            k = {"one": 1, "two": 2, "middle": (length + 1) // 2, "all_but_one": length - 1, "all": length}[which]
+            case.update(k=max(1, min(k, length)), k_class=which)
+        elif self._pick("dim_none", [True, False, False]):
+            case.update(dim=None, keepdim=False)
+            if _numel(shape) != length:  # (all elements are one row: the drawn length is the row's)
+                case.update(shape=[length], layout=self._layout([length]))
+        return case
+
+    def _quantile(self, op: str, dtype: str, length=None) -> dict:
+        rng = self.rng
+        if length is None:
+            length = self._select_length(dtype, "quantile")
+            shape, dim = self._rows_shape(length)
+        else:
+            shape, dim = ([length], 0) if rng.integers(2) else ([2, length], -1)
+        kind = self._pick("q", Q_KINDS)
+        count = int(kind[1:]) if kind.startswith("t") else 1
+        qs = [[0.0, 1.0, 0.5, 0.25][int(rng.integers(4))] if rng.integers(3) == 0 else float(np.float32(rng.random())) for _ in range(count)]
+        case = {"op": op, "dtype": dtype, "shape": shape, "dim": dim, "keepdim": self._pick("keepdim", [False, True]), "layout": self._layout(shape),
+                "dist": self._pick("quantile_dist", ["normal", "small_ints", "near_one"]), "nans": self._pick("nans_quantile", NAN_KINDS), "q_kind": kind, "qs": qs,
+                "interpolation": self._pick("interpolation", INTERPOLATIONS)}
+        if self._pick("dim_none", [True, False, False]):
+            case["dim"] = None
+            if _numel(shape) != length:  # (all elements are one row: the drawn length is the row's)
+                case.update(shape=[length], layout=self._layout([length]))
+        return case
+
+    # -- counting ---------------------------------------------------------------------------------------------------------------
+    def _edge_or(self, name: str, cut: int, cap: int) -> int:
+        """cut - 1, cut, cut + 1 or a random length up to the cap, each once in four draws of `name`: for the ops with few cases a round."""
+        step = self._pick(name, [-1, 0, 1, None])
+        return cut + step if step is not None else int(self.rng.integers(1, cap + 1))
+
+    def _bins(self, counter: int) -> int:
+        """A number of bins: the LDS tier's cut for this counter width - 1, + 0, + 1 (4-byte counters: or anywhere, once in four)."""
+        cut = self.t.bincount[counter]
+        step = self._pick(f"bins{counter}", [-1, 0, 1] + ([None] if counter == 4 else []))
+        return cut + step if step is not None else int(self.rng.integers(1, 3 * self.t.bincount[4] + 1))
+
+    def _bincount(self, dtype: str, bins=None, n=None) -> dict:
+        rng = self.rng
+        wide = dtype in ("int32", "int64")  # (the largest element is bins - 1: the cuts lie within these dtypes' range only)
+        wide = "large" if bins is not None else wide
+        weights = self._pick(f"bincount_weights_{wide}", BINCOUNT_WEIGHTS)
+        counter = 8 if weights not in (None, "float32") else 4
+        most = {"uint8": 256, "int8": 128, "int16": 32768}.get(dtype, 1 << 40)
+        how = self._pick(f"minlength_{wide}", ["zero", "below", "above"])
+        if bins is None:
+            bins = self._bins(counter) if wide else int(rng.integers(1, min(most, 300) + 1))  # (the bins the call counts into)
+            n = 0 if not wide and self._pick("bincount_empty", [False] * 5 + [True]) else int(rng.integers(1, SMALL_ELEMENTS // 2))
+            if how == "above" and n:  # (a minlength above the maximum: the data stays 17 below the drawn number of bins)
+                bins = max(bins - 17, 1)
+        minlength = {"zero": 0, "below": bins // 2, "above": bins + 17}[how]
+        return {"op": "bincount", "dtype": dtype, "n": n, "bins": bins, "minlength": minlength, "num_bins": max(bins, minlength) if n else minlength,
+                "weights": weights, "value_class": self._pick("class", ["exact", "general"]) if weights else "count", "layout": self._layout([n]),
+                "w_layout": self._layout([n])}
+
+    def _histc(self, dtype: str) -> dict:
+        rng = self.rng
+        rule = self._pick("histc_range", ["exact", "explicit", "data", "constant"])
+        shape = self._any_shape(int(rng.integers(1, SMALL_ELEMENTS // 2)) if rule in ("data", "constant") or rng.integers(6) else 0)
+        case = {"op": "histc", "dtype": dtype, "shape": shape, "layout": self._layout(shape), "value_class": "general"}
+        if rule == "exact":  # integer-valued data, lo = 0, hi = 2^k, a power of two of bins: every operation of the rule is exact
+            k = int(rng.integers(3, 8))
+            case.update(bins=1 << int(rng.integers(0, k + 1)), lo=0.0, hi=float(1 << k), range="explicit", nans="none", value_class="exact")
+            return case
+        lo = round(float(rng.uniform(-3, 0)), 3)
+        lo, hi = (lo, lo + round(float(rng.uniform(0.5, 4)), 3)) if rule == "explicit" else (0.0, 0.0)
+        case.update(bins=self._bins(4), lo=lo, hi=hi, range=rule,
+                    nans=self._pick("nans", NAN_KINDS) if rule == "explicit" else "none")
+        return case
+
+    def _histogram(self, dtype: str) -> dict:
+        rng = self.rng
+        weight = self._turn("histogram_weight", [True, False])
+        # the edge tensor's length bins + 1 on both sides of where a sequence leaves the search's LDS tier: the cut - 1, + 0, + 1
+        step = self._pick("histogram_edges_" + dtype, [-2, -1, 0] + ([None] if dtype == "float64" else []))
+        bins = self.t.search[dtype][0] + step if step is not None else int(rng.integers(1, 3 * self.t.bincount[4]))
+        n = self.t.search[dtype][2] + int(rng.integers(-1, 2)) if rng.integers(3) == 0 else int(rng.integers(1, SMALL_ELEMENTS))
+        if dtype == "float64" and rng.integers(6) == 0:
+            n = 0
+        shape = self._any_shape(n)
+        kind = self._pick("histogram_bins", ["int", "int_range", "edges"])
+        case = {"op": "histogram", "dtype": dtype, "shape": shape, "layout": self._layout(shape), "bins": bins, "bins_kind": kind, "weight": weight,
+                "w_layout": self._layout(shape), "value_class": self._turn("class_histogram", ["general", "exact"]) if weight else "count"}
+        if kind == "int_range":
+            lo = round(float(rng.uniform(-2, 0)), 2)
+            case["range"] = [lo, lo + round(float(rng.uniform(0.5, 3)), 2)]
+        return case
+
+    def _any_shape(self, n: int) -> list:
+        """A 1-D to 3-D shape of n elements (about: n rounded down to a multiple of the leading sizes)."""
+        rng = self.rng
+        if n < 2 or rng.integers(2):
+            return [n]
+        a = int(rng.integers(1, 5))
+        return [a, n // a] if rng.integers(2) else [a, 1, n // a]
+
+    # -- reductions -------------------------------------------------------------------------------------------------------------
+    def _reduce_class(self, op: str, dtype: str, reduce: str) -> str:
+        if reduce in ("max", "min", "amax", "amin"):
+            return "any"
+        return "wrap" if dtype not in FLOATS else self._turn("class_" + op, ["general", "exact"])
+
+    def _segment_reduce(self, dtype: str, longest=None) -> dict:
+        rng = self.rng
+        large = longest is not None
+        # (planned, not shuffled: a round has two regular float cases -- the large ones take float16 and bfloat16 --, two integer ones and
+        # three or four large ones: sum and prod, mean and max, min)
+        if large:
+            reduce = self._turn("segment_reduce_large", ["min", "max"])
+        elif dtype in FLOATS:
+            reduce = self._turn("segment_reduce_float", ["sum", "prod", "mean", "max", "min"])
+        else:
+            reduce = self._turn("segment_reduce_int", ["mean", "max", "sum", "min", "prod"])
+        if large and dtype in ("float16", "bfloat16") and reduce in ("sum", "mean"):
+            reduce = "prod"  # (no sum of so many 16-bit terms is in either value class)
+        cls = self._reduce_class("segment_reduce", dtype, reduce)
+        if large and dtype in ("float16", "bfloat16") and reduce == "prod":
+            cls = "exact"
+        initial = self._pick("initial", [None, 2])
+        capped = cls in ("exact", "general") and not (cls == "exact" and reduce == "prod")
+        cap = terms_cap(dtype, cls, 1, 2) if capped else 1 << 40
+        if longest is None:  # (the cut's edges are drawn only where the value class of this dtype holds so many terms)
+            longest = int(rng.integers(1, min(cap, 20000) + 1))
+            if cap > self.t.reduce_levels[0] + 1 and rng.integers(8):
+                longest = self.t.reduce_levels[0] + self._pick("segment_edge", [-1, 0, 1])
+        longest = min(longest, cap)
+        num_segments = int(rng.integers(1, 5 if large else 200))
+        seed = self._seed()
+        n = int(segment_lengths(num_segments, longest, seed).sum())
+        width = max(1, min(40, SMALL_ELEMENTS // n)) if not large else 1
+        tail = [[], [1], [int(rng.integers(2, width + 1))] if width >= 2 else [], [2, 2] if width >= 4 else []][int(rng.integers(4))]
+        shape = [n] + tail
+        return {"op": "segment_reduce", "dtype": dtype, "shape": shape, "layout": self._layout(shape), "reduce": reduce, "initial": initial,
+                "bounds": self._pick("bounds", ["lengths", "offsets"]), "bounds_dtype": self._pick("index_dtype", ["int32", "int64"]), "num_segments": num_segments,
+                "longest": longest, "lengths_seed": seed, "value_class": cls}
+
+    def _by_destination(self, op: str, dtype: str, n=None, M=None, dest=None) -> dict:
+        rng, t = self.rng, self.t
+        reduce = "sum"
+        if op != "index_add":
+            names = (["sum"] if op == "scatter_reduce" else []) + ["prod", "mean", "amax", "amin"]
+            reduce = self._turn(op + "_float", names) if dtype in FLOATS else self._turn(op + "_int", names[::-1])
+        cls = self._reduce_class(op, dtype, reduce)
+        alpha = self._pick("alpha", [1, 2]) if op == "index_add" else 1
+        include_self = True if op == "index_add" else self._pick("include_self", [True, False])
+        large = n is not None
+        if large:
+            if dtype == "float32":
+                cls = "exact"  # (millions of float32 terms to one destination: t * u < 0.1 does not hold)
+            shape, dim = [M], 0
+        else:
+            # (a general sum or product: several terms to one destination, which is what its bound is about)
+            dest = self._pick("destinations_general", ["equal", "zipf"]) if cls == "general" else self._pick("destinations", DESTINATIONS)
+            n = self._short_or("contributions", t.form_cuts[4, 1] + [t.search["int32"][0]], SMALL_ELEMENTS // 2)
+            size = self._pick("destination_count", ["few", "some", "index_edge"])
+            M = {"few": int(rng.integers(1, 51)), "some": int(rng.integers(51, 5000)), "index_edge": t.search["int32"][2] + self._pick("index_edge", [-1, 0, 1]) - 1}[size]
+            if dest != "distinct" and cls in ("exact", "general") and not (cls == "exact" and reduce == "prod") and n > terms_cap(dtype, cls, 2, 4):
+                # more terms to one destination than the value class of this dtype holds: in turn, as many as it holds, or distinct destinations
+                if self._pick("too_many_terms", ["fewer", "distinct"]) == "fewer":
+                    n = max(2, terms_cap(dtype, cls, 2, 4))
+                else:
+                    dest = "distinct"
+            if dest == "distinct":
+                M = max(M, n)
+            width = max(1, min(8, SMALL_ELEMENTS // max(M, n)))
+            other = [] if op == "scatter_reduce" or width < 2 else [[], [int(rng.integers(1, width + 1))], [2, width // 2] if width >= 4 else [1]][int(rng.integers(3))]
+            dim = int(rng.integers(len(other) + 1))
+            shape = other[:dim] + [M] + other[dim:]
+        source_shape = shape[:dim] + [n + (self._pick("src_extra", [0, 3]) if op == "scatter_reduce" else 0)] + shape[dim + 1:]
+        return {"op": op, "dtype": dtype, "shape": shape, "dim": dim, "layout": self._layout(shape), "source_shape": source_shape,
+                "source_layout": self._layout(source_shape), "n": n, "M": M, "destinations": dest, "index_dtype": self._pick("index_dtype", ["int32", "int64"]),
+                "index_layout": self._layout([n]), "reduce": reduce, "include_self": include_self, "alpha": alpha, "value_class": cls}
+
+    # -- scans ------------------------------------------------------------------------------------------------------------------
+    def _scan(self, op: str, dtype: str, length=None, target="draw") -> dict:
+        rng = self.rng
+        arith = op in ("cumsum", "cumprod")
+        if target == "draw":
+            target = self._pick("target_" + dtype, SCAN_TARGETS[dtype]) if arith else None
+        out = target or (dtype if dtype in FLOATS or not arith else "int64")
+        cls = "any" if not arith else "wrap" if out not in FLOATS else self._pick("class_" + op, ["general", "exact"])
+        if length is None:
+            kernel_in = dtype if dtype != "bool" else "uint8"
+            cuts = self.t.scan_cuts("int32", "int64", op)[:1] if arith else self.t.scan_cuts(kernel_in, kernel_in, op)[:1]
+            length = self._short_or("scan", cuts + [self.t.scan_levels[0]], SMALL_ELEMENTS // 2)
+            if cls in ("exact", "general") and not (cls == "exact" and op == "cumprod"):
+                length = min(length, terms_cap(out, cls, 1, 1))
+            shape, dim = self._rows_shape(length)
+            if rng.integers(16) == 0:
+                shape, dim = [[0], [3, 0], [0, 4]][int(rng.integers(3))], 0
+        else:
+            shape, dim = [length], 0
+        return {"op": op, "dtype": dtype, "shape": shape, "dim": dim, "layout": self._layout(shape), "out_dtype": target, "value_class": cls,
+                "dist": self._value_dist(dtype)}
+
+    # -- compaction -------------------------------------------------------------------------------------------------------------
+    def _tiles(self, cap: int = SMALL_ELEMENTS) -> int:
+        tile = self.t.compact_tile
+        return self._short_or("compact", [tile, 2 * tile, 5 * tile], cap)
+
+    def _compact(self, op: str, dtype: str, n=None) -> dict:
+        rng = self.rng
+        case = {"op": op, "dtype": dtype, "mask_class": self._pick("mask", MASK_CLASSES), "dist": self._value_dist(dtype)}
+        large = n is not None
+        if op in ("nonzero", "argwhere", "count_nonzero"):
+            shape = [n] if large else self._any_shape(self._tiles()) if rng.integers(12) else [[], [0], [2, 0]][int(rng.integers(3))]
+            case.update(shape=shape, layout=self._layout(shape))
+            if op == "nonzero":
+                case["as_tuple"] = self._pick("as_tuple", [False, True])
+        elif op in ("masked_select", "masked_scatter"):
+            n = n or self._tiles()
+            a = 1 if large else int(rng.integers(1, 5))
+            full = [a, max(n // a, 1)]
+            how = "same" if large else self._pick("broadcast", ["same", "mask", "x", "same"])
+            lower = [1, full[1]] if rng.integers(2) else [full[0], 1]
+            case.update(shape=lower if how == "x" else full, mask_shape=lower if how == "mask" else full, broadcast=how)
+            case.update(layout=self._layout(case["shape"]), mask_layout=self._layout(case["mask_shape"]))
+        else:
+            width = self._pick("row_width", ROW_WIDTHS)
+            rows = max(1, min(self._tiles(), SMALL_ELEMENTS // width))
+            lead = [rows] if self._pick("mask_dims", [1, 2]) == 1 else [int(rng.integers(1, 4)), max(rows // 3, 1)]
+            tail = {1: [[], [1]], 3: [[3]], 4: [[4], [2, 2]], 1025: [[1025], [5, 205]]}[width]
+            shape = lead + tail[int(rng.integers(len(tail)))]
+            case.update(shape=shape, mask_shape=lead, row_width=width, layout=self._layout(shape), mask_layout=self._layout(lead))
+            if op == "mask_index_put":
+                case["values"] = self._pick("put_values", ["exact", "broadcast", "scalar"])
+        return case
+
+    # -- the large minority -----------------------------------------------------------------------------------------------------
+    def _large_newer(self) -> list:
+        rng, t = self.rng, self.t
+        kind = self.large_newer.draw()
+        draw = lambda op, dtypes=None: self.new_op_dtype.draw(lambda p: p[0] == op and (dtypes is None or p[1] in dtypes))[1]  # noqa: E731
+        pool_min = t.pool_min_pairs or t.pool_min  # (pairs reach the pool form only above the cap: the bare keys' minimum stands in)
+        if kind == "index_add_skewed":
+            n = int(rng.integers(pool_min + 2, min(pool_min * 5 // 4, LARGE_ELEMENTS)))
+            dtype = self._preferred("index_add", ("int32", "int64"), ("int32", "int64", "float32", "float64"))
+            case = self._by_destination("index_add", dtype, n=n, M=int(rng.integers(2, 51)), dest="zipf")
+        elif kind == "index_add_pool_edge":
+            n = pool_min + self._pick("pool_edge", [-1, 0, 1])
+            # (one term and the input to a destination: every dtype's sum is in its value class; float32 and float64 are left to the regular cases)
+            dtype = self._preferred("index_add", ("float16", "bfloat16"), ("float16", "bfloat16", "int32", "int64"))
+            case = self._by_destination("index_add", dtype, n=n, M=n + int(rng.integers(0, 100)), dest="distinct")
+        elif kind == "cumsum_single_pass":
+            dtype = self._preferred("cumsum", ("int32", "float32"))
+            length = t.scan_cuts(dtype, dtype, "cumsum")[1] + self._pick("single_pass_edge", [-1, 0, 1])
+            case = self._scan("cumsum", dtype, length=length, target="int32" if dtype == "int32" else None)
+            if dtype == "float32":
+                case["value_class"] = "exact"
+        elif kind == "reduce_three_levels":
+            # (float16 / bfloat16 first: no sum of so many of their terms is in a value class, so their regular cases cannot draw the cut's edges)
+            case = self._segment_reduce(self._preferred("segment_reduce", ("float16", "bfloat16"), ("int32", "int64")), longest=t.reduce_levels[1] + self._pick("level_edge", [-1, 0, 1]))
+        elif kind == "kthvalue_grid":
+            dtype = draw("kthvalue")
+            case = self._select("kthvalue", dtype, length=t.select[dtype][1] + self._pick("grid_edge", [-1, 0, 1, 1000]))
+        elif kind == "quantile_grid":
+            op = self._pick("quantile_grid", list(QUANTILE_OPS))
+            dtype = draw(op)
+            case = self._quantile(op, dtype, length=t.select[dtype][1] + self._pick("grid_edge", [-1, 0, 1, 1000]))
+        elif kind == "bincount_global":
+            case = self._bincount(["int32", "int64"][int(rng.integers(2))], bins=1 << 20, n=int(rng.integers(1 << 20, 1 << 21)))
+        elif kind == "masked_select_large":
+            case = self._compact("masked_select", draw("masked_select"), n=LARGE_ELEMENTS)
+        else:
+            case = self._compact("nonzero", draw("nonzero"), n=LARGE_ELEMENTS)
+        return self._done(case, "large:" + kind)
+
+    def _next(self) -> list:
+        window, at = divmod(self._index, self.window)
+        if self._index % LARGE_EVERY == LARGE_AT:
+            return self._large_newer()
+        if window % 2 == 0 and at == 0:
+            return self._pending_sort()
+        if window % 2 == 1 and at == self.window - 1:
+            return self._neighbour()
+        op, dtype = self.new_op_dtype.draw()
+        if op in SELECT_OPS:
+            case = self._select(op, dtype)
+        elif op in QUANTILE_OPS:
+            case = self._quantile(op, dtype)
+        elif op in COUNT_OPS:
+            case = {"bincount": self._bincount, "histc": self._histc, "histogram": self._histogram}[op](dtype)
+        elif op == "segment_reduce":
+            case = self._segment_reduce(dtype)
+        elif op in REDUCE_OPS:
+            case = self._by_destination(op, dtype)
+        elif op in SCAN_OPS:
+            case = self._scan(op, dtype)
+        else:
+            case = self._compact(op, dtype)
+        return self._done(case)
+
+
+def _numel(shape) -> int:
+    out = 1
+    for v in shape:
+        out *= v
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the newer deck: its inputs (torch on the CPU and numpy; nothing of the library)
+
+def newer_values(name: str, shape, kind: str, seed: int):
+    """A contiguous CPU tensor of `shape`: a distribution of make_values, or "small_ints" (-1, 0, 1: exact sums), "signs" (+-1: exact
+    products), "normal" (finite, general sums), "near_one" (general products), "counts" (0 .. 100).  bool: random bits whatever the kind."""
+    import torch
+    rng = np.random.Generator(np.random.PCG64(seed))
+    shape = list(shape)
+    unsigned = name in ("uint8", "bool")
+    if name == "bool":
+        return torch.from_numpy(rng.integers(0, 2, size=shape).astype(np.bool_))
+    if kind == "small_ints":
+        return torch.from_numpy(rng.integers(0 if unsigned else -1, 2, size=shape)).to(torch_dtype(name))
+    if kind == "signs":
+        return torch.from_numpy(np.ones(shape, dtype=np.int64) if unsigned else rng.integers(0, 2, size=shape) * 2 - 1).to(torch_dtype(name))
+    if kind == "normal":
+        if name in FLOATS:
+            return torch.from_numpy(rng.standard_normal(shape)).to(torch_dtype(name))
+        return torch.from_numpy(rng.integers(0 if unsigned else -50, 51, size=shape)).to(torch_dtype(name))
+    if kind.startswith("near_one"):
+        if name in FLOATS:
+            terms = int(kind.split(":")[1]) if ":" in kind else 20
+            return torch.from_numpy(1.0 + np.clip(rng.standard_normal(shape), -5, 5) / terms).to(torch_dtype(name))
+        return torch.from_numpy(rng.integers(0, 2, size=shape) * 2 + (1 if unsigned else -1)).to(torch_dtype(name))  # (odd: a wrapping product is never 0)
+    return make_values(name, shape, kind, seed)
+
+
+def put_nans(t, dim, kind: str, seed: int):
+    """NaNs of `kind` (NAN_KINDS) into the float tensor t, whose rows run along dim (None: all of it one row)."""
+    import torch
+    rng = np.random.Generator(np.random.PCG64(seed + 7))
+    if kind == "none" or not t.dtype.is_floating_point or t.numel() == 0:
+        return t
+    rows = t.reshape(1, -1) if dim is None or t.dim() == 0 else t.movedim(dim, -1).reshape(-1, t.shape[dim])
+    rows = rows.clone()
+    R, L = rows.shape
+    for r in rng.integers(0, R, size=max(1, R // 3)):
+        rows[int(r), torch.from_numpy(rng.integers(0, L, size=int(rng.integers(1, 4))))] = float("nan")
+    if kind == "row" and R > 1:
+        rows[int(rng.integers(R))] = float("nan")
+    if dim is None or t.dim() == 0:
+        return rows.reshape(t.shape)
+    moved = t.movedim(dim, -1)
+    return rows.reshape(moved.shape).movedim(-1, dim).contiguous()
+
+
+def make_mask(shape, cls: str, seed: int, tile: int):
+    """A bool CPU tensor of `shape` of one of MASK_CLASSES."""
+    import torch
+    rng = np.random.Generator(np.random.PCG64(seed + 11))
+    n = _numel(shape)
+    if cls in ("none", "all"):
+        flat = np.full(n, cls == "all")
+    elif cls in ("sparse", "half"):
+        flat = rng.random(n) < (1 / 64 if cls == "sparse" else 0.5)
+    else:  # set in one tile only
+        flat = np.zeros(n, dtype=bool)
+        first = int(rng.integers(0, max(-(-n // tile), 1))) * tile
+        flat[first:first + tile] = rng.random(len(flat[first:first + tile])) < 0.5
+    return torch.from_numpy(flat.astype(np.bool_)).reshape(list(shape))
+
+
+def _sum_kind(case: dict, product: bool) -> str:
+    cls = case["value_class"]
+    if product:  # (general: factors 1 + z / t for a product of up to t terms, so that it stays within e^+-5 whatever the layout repeats)
+        if case["op"] == "segment_reduce":
+            most = case["longest"]
+        elif case["op"] in SCAN_OPS:
+            most = case["shape"][case["dim"]] if _numel(case["shape"]) else 1
+        else:
+            most = case["n"]
+        return {"exact": "signs", "general": f"near_one:{most + 1}", "wrap": "near_one"}.get(cls, "uniform")
+    return {"exact": "small_ints", "general": "normal", "wrap": "uniform"}.get(cls, "uniform")
+
+
+def destinations(kind: str, n: int, M: int, seed: int):
+    """n destinations in [0, M): all equal, distinct, or Zipf-like (destination 0 takes most, the far ones stay untouched)."""
+    rng = np.random.Generator(np.random.PCG64(seed + 13))
+    if kind == "equal":
+        return np.full(n, M // 3, dtype=np.int64)
+    if kind == "distinct":
+        return rng.permutation(M)[:n].astype(np.int64)
+    return np.minimum(rng.zipf(1.3, n) - 1, M - 1).astype(np.int64)
+
+
+def newer_inputs(case: dict) -> dict:
+    """name -> (base, view) as lay_out gives them, or a plain Python value: the inputs of a case of the newer ops, on the CPU."""
+    import torch
+    op, dtype, seed = case["op"], case["dtype"], case["data_seed"]
+    rng = np.random.Generator(np.random.PCG64(seed + 3))
+    tile = thresholds().compact_tile
+    out = {}
+
+    def laid(name, shape, layout, fill):
+        out[name] = lay_out(shape, layout, fill)
+
+    if op in SELECT_OPS or op in QUANTILE_OPS:
+        dim = case["dim"]
+        laid("x", case["shape"], case["layout"], lambda s: put_nans(newer_values(dtype, s, case["dist"], seed), dim, case["nans"], seed))
+        if op in QUANTILE_OPS and case["q_kind"] != "float":
+            q = torch.tensor(case["qs"], dtype=torch_dtype(dtype))
+            out["q"] = (q.reshape(()) if case["q_kind"] == "0d" else q, lambda t: t)
+    elif op == "bincount":
+        n, bins = case["n"], case["bins"]
+
+        def index(s):
+            x = rng.integers(0, bins, size=s[0])
+            x[rng.random(s[0]) < 0.3] = int(rng.integers(bins))  # (one hot bin)
+            if s[0]:
+                x[int(rng.integers(s[0]))] = bins - 1
+            return torch.from_numpy(x).to(torch_dtype(dtype))
+
+        laid("x", [n], case["layout"], index)
+        if case["weights"]:
+            laid("w", [n], case["w_layout"], lambda s: newer_values(case["weights"], s, _sum_kind(case, False), seed + 1))
+    elif op == "histc":
+        def data(s):
+            if case["value_class"] == "exact":
+                return torch.from_numpy(rng.integers(-2, int(case["hi"]) + 3, size=s)).to(torch_dtype(dtype))
+            if case["range"] == "constant":
+                return torch.full(s, 1.5, dtype=torch_dtype(dtype))
+            return put_nans(newer_values(dtype, s, "normal", seed), None, case["nans"], seed)
+
+        laid("x", case["shape"], case["layout"], data)
+    elif op == "histogram":
+        kind = case["bins_kind"]
+        edges = None
+        if kind == "edges":
+            steps = torch.from_numpy(np.abs(rng.standard_normal(case["bins"] + 1)) + 0.01)
+            edges = ((torch.cumsum(steps, 0) - steps.sum() / 2) * (6.0 / steps.sum())).to(torch_dtype(dtype))
+            out["edges"] = (edges, lambda t: t)
+
+        def data(s):
+            x = newer_values(dtype, s, "normal", seed)
+            marks = edges if edges is not None else torch.tensor(case["range"], dtype=x.dtype) if kind == "int_range" else None
+            if marks is not None and x.numel():  # a quarter of the elements exactly on an edge, the first and the last edge among them
+                hits = marks[torch.from_numpy(rng.integers(0, marks.numel(), size=x.numel()))].reshape(x.shape)
+                hits.reshape(-1)[:2] = marks[[0, -1]][:x.numel()]
+                x = torch.where(torch.from_numpy(rng.random(x.numel()) < 0.25).reshape(x.shape) | (torch.arange(x.numel()).reshape(x.shape) < 2), hits, x)
+            return x
+
+        laid("x", case["shape"], case["layout"], data)
+        if case["weight"]:
+            laid("w", case["shape"], case["w_layout"], lambda s: newer_values(dtype, s, _sum_kind(case, False), seed + 1))
+    elif op == "segment_reduce":
+        laid("x", case["shape"], case["layout"], lambda s: newer_values(dtype, s, _sum_kind(case, case["reduce"] == "prod"), seed))
+        lengths = torch.from_numpy(segment_lengths(case["num_segments"], case["longest"], case["lengths_seed"]))
+        bounds = lengths if case["bounds"] == "lengths" else torch.cat((torch.zeros(1, dtype=torch.int64), torch.cumsum(lengths, 0)))
+        out["bounds"] = (bounds.to(torch_dtype(case["bounds_dtype"])), lambda t: t)
+    elif op in REDUCE_OPS:
+        product = case["reduce"] == "prod"
+        base_kind = "signs" if product and case["value_class"] == "exact" else "counts4" if case["value_class"] == "exact" else _sum_kind(case, product)
+
+        def base(s):
+            if base_kind == "counts4":
+                return torch.from_numpy(rng.integers(0 if dtype == "uint8" else -4, 5, size=s)).to(torch_dtype(dtype))
+            return newer_values(dtype, s, base_kind, seed + 2)
+
+        laid("x", case["shape"], case["layout"], base)
+        laid("source", case["source_shape"], case["source_layout"], lambda s: newer_values(dtype, s, _sum_kind(case, product), seed))
+        laid("index", [case["n"]], case["index_layout"],
+             lambda s: torch.from_numpy(destinations(case["destinations"], case["n"], case["M"], seed)).to(torch_dtype(case["index_dtype"])))
+    elif op in SCAN_OPS:
+        kind = case["dist"] if case["value_class"] == "any" else _sum_kind(case, op == "cumprod")
+        laid("x", case["shape"], case["layout"], lambda s: newer_values(dtype, s, kind, seed))
+    elif op in ("nonzero", "argwhere", "count_nonzero"):
+        def flags(s):
+            x = newer_values(dtype, s, case["dist"], seed)
+            keep = make_mask(s, case["mask_class"], seed, tile)
+            x = torch.where(keep, x, torch.zeros((), dtype=x.dtype))
+            if x.dtype.is_floating_point:  # (-0.0 is zero)
+                x = torch.where(~keep & torch.from_numpy(rng.random(_numel(s)) < 0.1).reshape(s), torch.full((), -0.0, dtype=x.dtype), x)
+            return x
+
+        laid("x", case["shape"], case["layout"], flags)
+    else:
+        laid("x", case["shape"], case["layout"], lambda s: newer_values(dtype, s, case["dist"], seed))
+        laid("mask", case["mask_shape"], case["mask_layout"], lambda s: make_mask(s, case["mask_class"], seed, tile))
+        base, view = out["mask"]
+        mask = view(base)
+        if op == "masked_scatter":
+            R = int(torch.broadcast_tensors(mask, torch.empty(case["shape"]))[0].sum())
+            out["source"] = (newer_values(dtype, [R + int(rng.integers(0, 3))], case["dist"], seed + 1), lambda t: t)
+        elif op == "mask_index_put":
+            tail = case["shape"][len(case["mask_shape"]):]
+            shape = {"exact": [int(mask.sum())] + tail, "broadcast": [[1] + tail, tail][int(rng.integers(2))], "scalar": []}[case["values"]]
+            out["values"] = (newer_values(dtype, shape, case["dist"], seed + 1), lambda t: t)
+    return out
+
+
+def call_newer(api, case: dict, t: dict):
+    """The one public call of a case of the newer ops on `api`: this library, or anything with the same functions."""
+    op = case["op"]
+    if op == "kthvalue":
+        return api.kthvalue(t["x"], case["k"], case["dim"], case["keepdim"])
+    if op in ("median", "nanmedian"):
+        return getattr(api, op)(t["x"]) if case["dim"] is None else getattr(api, op)(t["x"], case["dim"], case["keepdim"])
+    if op in QUANTILE_OPS:
+        q = case["qs"][0] if case["q_kind"] == "float" else t["q"]
+        return getattr(api, op)(t["x"], q, case["dim"], case["keepdim"], interpolation=case["interpolation"])
+    if op == "bincount":
+        return api.bincount(t["x"], weights=t.get("w"), minlength=case["minlength"])
+    if op == "histc":
+        return api.histc(t["x"], bins=case["bins"], min=case["lo"], max=case["hi"])
+    if op == "histogram":
+        bins = t["edges"] if case["bins_kind"] == "edges" else case["bins"]
+        return api.histogram(t["x"], bins, range=tuple(case["range"]) if "range" in case else None, weight=t.get("w"))
+    if op == "segment_reduce":
+        return api.segment_reduce(t["x"], case["reduce"], **{case["bounds"]: t["bounds"]}, initial=case["initial"])
+    if op == "index_add":
+        return api.index_add(t["x"], case["dim"], t["index"], t["source"], alpha=case["alpha"])
+    if op == "index_reduce":
+        return api.index_reduce(t["x"], case["dim"], t["index"], t["source"], case["reduce"], include_self=case["include_self"])
+    if op == "scatter_reduce":
+        return api.scatter_reduce(t["x"], 0, t["index"], t["source"], case["reduce"], include_self=case["include_self"])
+    if op in ("cumsum", "cumprod"):
+        return getattr(api, op)(t["x"], case["dim"], dtype=torch_dtype(case["out_dtype"]) if case["out_dtype"] else None)
+    if op in ("cummax", "cummin"):
+        return getattr(api, op)(t["x"], case["dim"])
+    if op == "nonzero":
+        return api.nonzero(t["x"], as_tuple=case["as_tuple"])
+    if op in ("argwhere", "count_nonzero"):
+        return getattr(api, op)(t["x"])
+    if op == "masked_select":
+        return api.masked_select(t["x"], t["mask"])
+    if op == "masked_scatter":
+        return api.masked_scatter(t["x"], t["mask"], t["source"])
+    if op == "mask_index":
+        return api.mask_index(t["x"], t["mask"])
+    return api.mask_index_put(t["x"], t["mask"], t["values"])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the newer deck: its references (torch's CPU functions and numpy only) and the rules they are compared by
+
+class Want:
+    """One expected output: `rule` says how the returned tensor is held to `want`.
+       bits      the same dtype, shape and bits; for floats a NaN on both sides counts as equal
+       value     the same dtype and shape, == or NaN on both sides, and the same bits wherever `want` is neither zero nor NaN (the sign
+                 of a zero that an order leaves open: kthvalue's tie of -0.0 and +0.0, a maximum of the two, quantile's +0.0)
+       bound     the same dtype and shape, NaN where `want` (float64) is, and |returned - want| <= bound
+       index     int64 positions into `rows` along `dim`, in range, at which `rows` holds the returned values' bits (`values_at`: which output)"""
+
+    def __init__(self, name, want, rule="bits", **more):
+        self.name, self.want, self.rule = name, want, rule
+        self.__dict__.update(more)
+
+
+def as_count(counts, dtype):
+    """Integer counts (numpy) as a CPU tensor of the dtype, each the correctly rounded count."""
+    import torch
+    counts = np.asarray(counts, dtype=np.int64)
+    if dtype == torch.int64:
+        return torch.from_numpy(counts)
+    if dtype == torch.float16:
+        with np.errstate(over="ignore"):
+            return torch.from_numpy(counts.astype(np.float64).astype(np.float16))  # (exact in float64, then one rounding)
+    if dtype == torch.bfloat16:
+        assert counts.max(initial=0) < 1 << 24  # (exact in float32, then one rounding)
+        return torch.from_numpy(counts.astype(np.float32)).to(torch.bfloat16)
+    return torch.from_numpy(counts.astype(np.float32 if dtype == torch.float32 else np.float64))
+
+
+def _signed_view(t):
+    import torch
+    return t.contiguous().view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def _sum_wants(name, exact64, mass64, terms, dtype, value_class, same_dtype, divisor=None):
+    """A float sum as a Want: exact class `same_dtype` (torch's own result in the dtype) under ==; general class the float64 sum within
+    (t + 1) u sum|x| (a mean: that over the divisor, and one more u)."""
+    import torch
+    if value_class != "general":
+        return Want(name, same_dtype, "value")
+    u = EPS[str(dtype).split(".")[1]]
+    bound = (terms.double() + 1) * u * mass64
+    if divisor is not None:
+        d = divisor.double().clamp(min=1)
+        bound = (terms.double() + 2) * u * mass64 / d
+    return Want(name, exact64, "bound", bound=bound, dtype=dtype)
+
+
+def _select_reference(case, x):
+    import torch
+    op, dim = case["op"], case["dim"]
+    flat = x.reshape(-1) if dim is None else x
+    d = 0 if dim is None else dim
+    order = torch.sort(flat, dim=d, stable=True)
+    L = flat.shape[d]
+    nans = torch.isnan(flat).sum(d, keepdim=True) if flat.dtype.is_floating_point else torch.zeros_like(order.indices.narrow(d, 0, 1))
+    if op == "kthvalue":
+        j = torch.full_like(nans, case["k"] - 1)
+    elif op == "median":
+        j = torch.where(nans > 0, L - nans, torch.full_like(nans, (L - 1) // 2))
+    else:
+        j = torch.where(nans < L, (L - nans - 1) // 2, torch.zeros_like(nans))
+    idx = order.indices.gather(d, j)
+    val = _signed_view(flat).gather(d, idx).view(flat.dtype)
+    srt = order.values
+    free = ((srt.narrow(d, 1, L - 1) != srt.narrow(d, 0, L - 1)).all(d, keepdim=True) if L > 1 else torch.ones_like(nans, dtype=torch.bool)) & (nans == 0)
+    if dim is None:
+        return [Want("values", val.reshape(()), "value")]
+    keep = (lambda t: t) if case["keepdim"] else (lambda t: t.squeeze(d))
+    theirs = getattr(torch, op)(flat, *((case["k"],) if op == "kthvalue" else ()), d, True).indices
+    return [Want("values", keep(val), "value"),
+            Want("indices", keep(idx), "index", rows=flat, dim=d, keepdim=case["keepdim"], values_at=0, free=keep(free), theirs=keep(theirs))]
+
+
+def _histc_rule(x, bins: int, lo: float, hi: float):
+    """The rule of histc's docstring in numpy: bin = (int)((x - lo) * bins / (hi - lo)), each operation rounded on its own, in float32
+    (float64 for float64); bin == bins goes to the last bin; x < lo, x > hi and NaN are not counted."""
+    import torch
+    F = np.float64 if x.dtype == torch.float64 else np.float32
+    xs = x.to(torch.float64 if F is np.float64 else torch.float32).reshape(-1).numpy()
+    lo, hi = F(lo), F(hi)
+    with np.errstate(invalid="ignore", over="ignore"):
+        xs = xs[(xs >= lo) & (xs <= hi)]
+        q = ((xs - lo) * F(bins)) / (hi - lo)
+        at = np.where(q < F(4294967296.0), q, F(0)).astype(np.int64)
+        at = np.where(q < F(4294967296.0), np.minimum(at, bins - 1), bins - 1)
+    return np.bincount(at, minlength=bins)
+
+
+def _bin_sums(at, bins: int, w, case, dtype, name):
+    """Counts (no weights) or weighted sums per bin as a Want; `at`: numpy bin numbers, already filtered, w: the matching weights."""
+    import torch
+    counts = np.bincount(at, minlength=bins)
+    if w is None:
+        return Want(name, as_count(counts, dtype), "bits")
+    w64 = w.double().numpy()
+    exact = torch.from_numpy(np.bincount(at, weights=w64, minlength=bins))
+    mass = torch.from_numpy(np.bincount(at, weights=np.abs(w64), minlength=bins))
+    return _sum_wants(name, exact, mass, torch.from_numpy(counts), dtype, case["value_class"], exact.to(dtype))
+
+
+def _segment_ints(x, lengths, reduce: str, initial):
+    """segment_reduce of int32 / int64 rows in numpy, as the wrapper documents it: sums and products wrap, an empty max / min answers the
+    type's minimum / maximum, the mean is floored and 0 for an empty segment."""
+    import torch
+    info = np.iinfo(np.int32 if x.dtype == torch.int32 else np.int64)
+    rows = x.reshape(x.shape[0], -1).numpy()
+    out = np.empty((len(lengths), rows.shape[1]), dtype=rows.dtype)
+    at = 0
+    with np.errstate(over="ignore"):
+        for i, n in enumerate(lengths):
+            part = rows[at:at + n]
+            at += n
+            if reduce in ("sum", "mean"):
+                v = part.sum(0, dtype=rows.dtype) + rows.dtype.type(initial or 0)
+                out[i] = v // max(n, 1) if reduce == "mean" else v
+            elif reduce == "prod":
+                out[i] = part.prod(0, dtype=rows.dtype) * rows.dtype.type(1 if initial is None else initial)
+            else:
+                start = (info.min if reduce == "max" else info.max) if initial is None else initial
+                out[i] = (np.maximum if reduce == "max" else np.minimum)(part.max(0, initial=info.min) if reduce == "max" else part.min(0, initial=info.max), start)
+    return torch.from_numpy(out).reshape((len(lengths),) + tuple(x.shape[1:]))
+
+
+def reference_newer(case: dict, cpu: dict, got=None) -> list:
+    """The expected outputs of a case of the newer ops, in the order the call returns them: a list of Want.  `got` (the returned CPU
+    tensors) is read only where the expectation hangs on an output that is torch's and not a kernel's: histogram's linspace edges."""
+    import torch
+    op = case["op"]
+    x = cpu["x"].contiguous()
+    dtype = x.dtype
+    if op in SELECT_OPS:
+        return _select_reference(case, x)
+    if op in QUANTILE_OPS:
+        fn, q = getattr(torch, op), (case["qs"][0] if case["q_kind"] == "float" else cpu["q"])
+        want = fn(x, q, case["dim"], case["keepdim"], interpolation=case["interpolation"])
+        if case["interpolation"] in ("lower", "higher", "nearest"):
+            return [Want("quantiles", want, "value")]
+        lo, hi = (fn(x, q, case["dim"], case["keepdim"], interpolation=i) for i in ("lower", "higher"))
+        bound = 4 * EPS[case["dtype"]] * torch.maximum(lo.abs(), hi.abs()).double()
+        return [Want("quantiles", want.double(), "bound", bound=torch.where(torch.isnan(bound), torch.zeros_like(bound), bound), dtype=dtype, nan_as=want)]
+    if op == "bincount":
+        w = cpu.get("w")
+        if w is not None and w.dtype not in (torch.float32, torch.float64):
+            w = w.double()
+        out = torch.int64 if w is None else w.dtype
+        return [_bin_sums(x.numpy().astype(np.int64), case["num_bins"], w.contiguous() if w is not None else None, case, out, "counts")]
+    if op == "histc":
+        lo, hi = case["lo"], case["hi"]
+        if lo == hi and x.numel():
+            lo, hi = float(x.min()), float(x.max())
+        if lo == hi:
+            lo, hi = lo - 1.0, hi + 1.0
+        return [Want("counts", as_count(_histc_rule(x, case["bins"], lo, hi), dtype), "bits")]
+    if op == "histogram":
+        bins = case["bins"]
+        if case["bins_kind"] == "edges":
+            edges, edge_want = cpu["edges"], Want("bin_edges", cpu["edges"], "bits")
+        else:
+            lo, hi = case["range"] if "range" in case else ((float(x.min()), float(x.max())) if x.numel() else (0.0, 1.0))
+            if lo == hi:
+                lo, hi = lo - 0.5, hi + 0.5
+            exact = torch.linspace(lo, hi, bins + 1, dtype=torch.float64)
+            # (the edges are torch.linspace's on the device, not a kernel's: a step, a product and a sum, each rounded once)
+            edge_want = Want("bin_edges", exact, "bound", bound=torch.full_like(exact, 4 * EPS[case["dtype"]] * max(abs(lo), abs(hi))), dtype=dtype)
+            edges = got[1] if got is not None and len(got) > 1 and got[1].shape == exact.shape and got[1].dtype == dtype else exact.to(dtype)
+        e, xs = edges.numpy(), x.reshape(-1).numpy()
+        at = np.searchsorted(e, xs, side="right") - 1
+        at = np.where(xs == e[-1], bins - 1, at)
+        ok = (at >= 0) & (at < bins) & ~np.isnan(xs)
+        w = cpu["w"].contiguous().reshape(-1)[torch.from_numpy(ok)] if "w" in cpu else None
+        return [_bin_sums(at[ok], bins, w, case, dtype, "hist"), edge_want]
+    if op == "segment_reduce":
+        lengths = segment_lengths(case["num_segments"], case["longest"], case["lengths_seed"])
+        reduce, initial, cls = case["reduce"], case["initial"], case["value_class"]
+        kw = {case["bounds"]: cpu["bounds"].long()}
+        if not dtype.is_floating_point:
+            return [Want("out", _segment_ints(x, lengths, reduce, initial), "bits")]
+        same = torch.segment_reduce(x, reduce, initial=initial, **kw)
+        if cls != "general":
+            return [Want("out", same, "value")]
+        exact = torch.segment_reduce(x.double(), reduce, initial=initial, **kw)
+        terms = torch.from_numpy(lengths + (initial is not None)).reshape((-1,) + (1,) * (x.dim() - 1))
+        if reduce == "prod":
+            return [_product_want("out", exact, terms, dtype)]
+        mass = torch.segment_reduce(x.double().abs(), "sum", initial=abs(initial) if initial is not None else None, **kw)
+        want = _sum_wants("out", exact, mass, terms, dtype, cls, same, torch.from_numpy(lengths).reshape(terms.shape) if reduce == "mean" else None)
+        want.nan_as = same  # (a mean of no rows without an initial: NaN)
+        return [want]
+    if op in REDUCE_OPS:
+        return [_by_destination_reference(case, x, cpu["index"].contiguous().long(), cpu["source"].contiguous())]
+    if op in ("cumsum", "cumprod"):
+        target = torch_dtype(case["out_dtype"]) if case["out_dtype"] else None
+        same = getattr(torch, op)(x, case["dim"], dtype=target)
+        if case["value_class"] != "general":
+            return [Want("out", same, "value" if same.dtype.is_floating_point else "bits")]
+        xt = x.to(same.dtype).double()
+        exact = getattr(torch, op)(xt, case["dim"])
+        terms = (torch.arange(x.shape[case["dim"]]) + 1).reshape([-1 if d == case["dim"] % x.dim() else 1 for d in range(x.dim())]).expand(x.shape)
+        if op == "cumprod":
+            return [_product_want("out", exact, terms, same.dtype)]
+        return [_sum_wants("out", exact, torch.cumsum(xt.abs(), case["dim"]), terms, same.dtype, "general", same)]
+    if op in ("cummax", "cummin"):
+        values, indices = getattr(torch, op)(x, case["dim"])
+        return [Want("values", values, "bits"), Want("indices", indices, "bits")]
+    if op == "nonzero":
+        r = torch.nonzero(x, as_tuple=case["as_tuple"])
+        return [Want(f"dim {i}", c.contiguous(), "bits") for i, c in enumerate(r)] if case["as_tuple"] else [Want("coordinates", r, "bits")]
+    if op == "argwhere":
+        return [Want("coordinates", torch.argwhere(x), "bits")]
+    if op == "count_nonzero":
+        return [Want("count", torch.count_nonzero(x), "bits")]
+    mask = cpu["mask"]
+    if op == "masked_select":
+        return [Want("selected", torch.masked_select(x, mask), "bits")]
+    if op == "masked_scatter":
+        full = torch.broadcast_tensors(x, mask)[0].contiguous()
+        return [Want("out", full.masked_scatter(mask, cpu["source"]), "bits")]
+    if op == "mask_index":
+        return [Want("rows", x[mask], "bits")]
+    return [Want("out", torch.index_put(x, (mask,), cpu["values"]), "bits")]
+
+
+def _product_want(name, exact64, terms, dtype):
+    """A float product of t terms: relative error at most t u / (1 - t u).  (The generator keeps a general product of t factors within
+    e^+-5 of the first one, far from the dtype's denormals and from its largest value, where this bound would not hold.)"""
+    tu = terms.double() * EPS[str(dtype).split(".")[1]]
+    return Want(name, exact64, "bound", bound=(tu / (1 - tu)) * exact64.abs(), dtype=dtype)
+
+
+def _by_destination_reference(case, x, index, source):
+    import torch
+    op, dim, reduce, cls = case["op"], case["dim"], case["reduce"], case["value_class"]
+    include_self, alpha, M = case["include_self"], case["alpha"], case["M"]
+
+    def run(base, src):
+        if op == "index_add":
+            return torch.index_add(base, dim, index, src, alpha=alpha)
+        if op == "index_reduce":
+            return torch.index_reduce(base, dim, index, src, reduce, include_self=include_self)
+        return torch.scatter_reduce(base, 0, index, src[:index.numel()], reduce, include_self=include_self)
+
+    if cls != "general":
+        if reduce == "prod" and x.dtype in (torch.float16, torch.bfloat16):
+            # (torch's CPU index_reduce fails an internal assertion on some 16-bit shapes; products of +-1 are exact in float32 as well)
+            return Want("out", run(x.float(), source.float()).to(x.dtype), "value")
+        return Want("out", run(x, source), "value" if x.dtype.is_floating_point else "bits")
+    exact = run(x.double(), source.double())
+    count = torch.bincount(index, minlength=M).reshape([-1 if d == dim else 1 for d in range(x.dim())])
+    terms = (count + (1 if include_self else 0)).expand(x.shape)
+    if reduce == "prod":
+        return _product_want("out", exact, terms, x.dtype)
+    src_abs = source.double().abs() * alpha
+    if op == "scatter_reduce":
+        mass = torch.scatter_reduce(x.double().abs(), 0, index, src_abs[:index.numel()], "sum", include_self=include_self)
+    else:
+        mass = torch.index_add(x.double().abs() if include_self else torch.where(count.expand(x.shape) > 0, 0.0, x.double().abs()), dim, index, src_abs)
+    return _sum_wants("out", exact, mass, terms, x.dtype, cls, None, terms if reduce == "mean" else None)
+
+
+def _hold(w: Want, g, got: list):
+    """None when the returned tensor g meets the Want, else the line that says where it does not."""
+    import torch
+    want, rule = w.want, w.rule
+    dtype = getattr(w, "dtype", want.dtype)
+    if g.dtype != dtype or g.shape != want.shape:
+        return f"{w.name}: {g.dtype} {tuple(g.shape)} returned, {dtype} {tuple(want.shape)} expected"
+    if g.numel() == 0:
+        return None
+
+    def at(bad, what):
+        flat = int(torch.nonzero(bad.reshape(-1))[0])
+        pos = tuple(int(i) for i in np.unravel_index(flat, tuple(g.shape))) if g.dim() else ()
+        return (f"{w.name}: {what} at {pos} (flat {flat}) of {g.numel()}: returned {g.reshape(-1)[flat].item()!r}, expected "
+                f"{want.reshape(-1)[flat].item()!r}; {int(bad.sum())} elements differ")
+
+    if rule == "bits":
+        if g.dtype.is_floating_point:
+            both = torch.isnan(g) & torch.isnan(want)
+            g = torch.where(both, torch.zeros_like(g), g)
+            want = torch.where(both, torch.zeros_like(want), want)
+        return _first_difference(w.name, g, want)
+    if rule == "value":
+        if not g.dtype.is_floating_point:
+            return _first_difference(w.name, g, want)
+        both = torch.isnan(g) & torch.isnan(want)
+        bad = ~both & ~(g == want)
+        plain = ~torch.isnan(want) & (want != 0)
+        bad |= plain & (_signed_view(g) != _signed_view(want))
+        return at(bad, "another value") if bool(bad.any()) else None
+    if rule == "bound":
+        nan_as = getattr(w, "nan_as", None)
+        expect_nan = torch.isnan(nan_as) if nan_as is not None else torch.isnan(want)
+        bad = torch.isnan(g) != expect_nan
+        err = (g.double() - want).abs()
+        inf = torch.isinf(want)
+        bad |= ~expect_nan & torch.where(inf, g.double() != want, ~(err <= w.bound))
+        if bool(bad.any()):
+            flat = int(torch.nonzero(bad.reshape(-1))[0])
+            return at(bad, f"beyond the bound {w.bound.reshape(-1)[flat].item():.3e}")
+        return None
+    if rule == "index":
+        L = w.rows.shape[w.dim]
+        if g.dtype != torch.int64:
+            return f"{w.name}: {g.dtype} returned, int64 expected"
+        bad = (g < 0) | (g >= L)
+        if bool(bad.any()):
+            return at(bad, "out of range")
+        values = got[w.values_at]
+        gi, gv = (g, values) if w.keepdim else (g.unsqueeze(w.dim), values.unsqueeze(w.dim))
+        bad = _signed_view(w.rows).gather(w.dim, gi) != _signed_view(gv)
+        if bool(bad.any()):
+            return f"{w.name}: the row does not hold the returned value at {int(bad.sum())} returned positions"
+        bad = w.free & (g != w.theirs)  # (torch's own index, where no tie leaves it open)
+        return at(bad, "another index than torch's on a row without ties") if bool(bad.any()) else None
+    raise ValueError(rule)
+
+
+def check_newer(case: dict, cpu: dict, got: list) -> list:
+    import torch
+    wants = reference_newer(case, cpu, got)
+    if len(got) != len(wants):
+        return [f"{len(got)} outputs returned, {len(wants)} expected"]
+    bad = [line for line in (_hold(w, g, got) for w, g in zip(wants, got)) if line]
+    if not bad and case["op"] == "histc" and case["value_class"] == "exact":  # torch's own, where its arithmetic is exact too
+        x = cpu["x"]
+        theirs = torch.histc(x.double() if x.dtype == torch.float64 else x.float(), case["bins"], case["lo"], case["hi"])
+        line = _first_difference("counts against torch.histc", got[0], as_count(theirs.long().numpy(), x.dtype))
+        bad += [line] if line else []
+    return bad
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # the runner
 
 class Mismatch(AssertionError):
@@ -737,6 +1835,14 @@ def prepare(case: dict, device):
     stream.  A dependent searchsorted gets its queries only: its sequence is a library result that launch() picks up."""
     import torch
     op = case["op"]
+    if op in NEWER_OPS:
+        cpu, gpu = {}, {}
+        for name, item in newer_inputs(case).items():
+            base, view = item
+            cpu[name] = view(base)
+            if device is not None:
+                gpu[name] = view(base.to(device))
+        return cpu, gpu
     if op not in ("searchsorted", "bucketize"):
         base, view = lay_out(case["shape"], case["layout"], lambda s: make_values(case["dtype"], s, case["dist"], case["data_seed"]))
         return {"x": view(base)}, {"x": view(base.to(device))}
@@ -785,6 +1891,8 @@ def launch(case: dict, gpu: dict, results: dict):
     """One call of the public API; returns its result as it came.  No copy between host and device is made here."""
     import vkradixsort_amd as vrs
     op = case["op"]
+    if op in NEWER_OPS:
+        return call_newer(vrs, case, gpu)
     if case.get("variant") == "dependent":
         gpu["seq"] = results[case["source"]]  # what an earlier sort / unique of this window returned, possibly still being computed
     if op == "sort":
@@ -818,6 +1926,8 @@ def check(case: dict, cpu: dict, result) -> list:
     import torch
     op = case["op"]
     got = [t.cpu() for t in _as_tuple(result)]
+    if op in NEWER_OPS:
+        return check_newer(case, cpu, got)
     bad = []
 
     def same(name, g, w):
@@ -878,19 +1988,19 @@ def check(case: dict, cpu: dict, result) -> list:
     return bad
 
 
-def replay_line(seed: int, index: int) -> str:
-    return f"python tools/fuzz_ops.py 0 {seed} --count {index + 1}"
+def replay_line(seed: int, index: int, deck: str = "first") -> str:
+    return f"python tools/fuzz_ops.py 0 {seed} --count {index + 1}" + ("" if deck == "first" else f" --deck {deck}")
 
 
 def _report(seed: int, index: int, recent: list, what: list) -> str:
     lines = [f"fuzz_ops: seed {seed}, case {index} FAILED"] + [f"  {w}" for w in what]
     lines += ["the last cases (the failing one last):"] + ["  " + json.dumps(c, sort_keys=True) for c in recent[-8:]]
-    lines.append("replay: " + replay_line(seed, index))
+    lines.append("replay: " + replay_line(seed, index, recent[-1].get("deck", "first") if recent else "first"))
     return "\n".join(lines)
 
 
-def run(seed: int, count: int, device=None, window: int = 4, seconds=None, quiet: bool = True) -> int:
-    """Runs the first `count` cases of `seed` (or as many as `seconds` allow) and returns how many ran and passed.  The inputs of a
+def run(seed: int, count: int, device=None, window: int = 4, seconds=None, quiet: bool = True, deck: str = "first") -> int:
+    """Runs the first `count` cases of `seed` in `deck` (or as many as `seconds` allow) and returns how many ran and passed.  The inputs of a
     whole window are made and uploaded first, on a stream of their own, so that nothing waits for the streams the library works on;
     then the window's calls go out back to back on torch's current stream -- every fifth window on a second stream -- with no copy and
     no synchronisation between them, while the window before has not been looked at yet; that one is checked afterwards.  The first
@@ -948,7 +2058,7 @@ def run(seed: int, count: int, device=None, window: int = 4, seconds=None, quiet
                     results[case["index"]] = _as_tuple(out)[0]  # what a dependent searchsorted of this window may search
                 pending.append(_Pending(case, stream, cpu, out, _nbytes(list(gpu.values()), _as_tuple(out))))
 
-    for _, group in itertools.groupby(cases(seed, count, window), key=lambda c: c["window"]):
+    for _, group in itertools.groupby(cases(seed, count, window, deck), key=lambda c: c["window"]):
         if seconds is not None and time.monotonic() - started > seconds:
             break
         group = list(group)
@@ -985,15 +2095,16 @@ def main(argv) -> int:
     ap.add_argument("seconds", type=float, help="time budget of a soak (0 with --count)")
     ap.add_argument("seed", type=int)
     ap.add_argument("--count", type=int, default=None, help="run exactly the first COUNT cases instead of a time budget")
+    ap.add_argument("--deck", default="first", choices=["first", "newer"], help="which ops: the first deck's, or the newer ops among them")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
     t0 = time.monotonic()
     if args.count is not None:
-        done = run(args.seed, args.count, args.device, quiet=not args.verbose)
+        done = run(args.seed, args.count, args.device, quiet=not args.verbose, deck=args.deck)
     else:
-        done = run(args.seed, 1 << 30, args.device, seconds=args.seconds, quiet=not args.verbose)
-    print(f"fuzz_ops: seed {args.seed}: {done} cases passed in {time.monotonic() - t0:.1f} s")
+        done = run(args.seed, 1 << 30, args.device, seconds=args.seconds, quiet=not args.verbose, deck=args.deck)
+    print(f"fuzz_ops: seed {args.seed}, deck {args.deck}: {done} cases passed in {time.monotonic() - t0:.1f} s")
     return 0
 
 

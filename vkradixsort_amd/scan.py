@@ -43,13 +43,16 @@ def scan_stats(ctx) -> dict:
     return stats
 
 
-def _check(name: str, x, dim: int) -> int:
+def _check(name: str, x, dim: int, coded: bool = False) -> int:
+    """What is refused before any device work: the dtype first (coded: one the kernel has a code for, bool as uint8), then the device, the dim."""
     import torch
 
     if not isinstance(x, torch.Tensor):
         _refuse(f"{name} takes a tensor")
     if x.dtype.is_complex:
         _refuse(f"{name} takes no complex dtype")
+    if coded:
+        _dtype_code(torch, torch.uint8 if x.dtype == torch.bool else x.dtype, name)
     _on_gpu(name, x)
     nd = max(x.dim(), 1)
     if not isinstance(dim, int) or not -nd <= dim < nd:
@@ -116,9 +119,8 @@ def cumprod(x, dim: int, *, dtype=None):
 def _pairs(name: str, x, dim: int, op: int):
     import torch
 
-    dim = _check(name, x, dim)
+    dim = _check(name, x, dim, coded=True)
     src = x.to(torch.uint8) if x.dtype == torch.bool else x
-    _dtype_code(torch, src.dtype, name)
     values, indices = _scan_rows(src, dim, op, src.dtype)
     return getattr(torch.return_types, name)((values.to(x.dtype), indices))
 

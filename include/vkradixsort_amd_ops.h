@@ -277,8 +277,8 @@ int vrs_quantile_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_
  * [0, boundary_row_len] per query, no fault.  sorter: NULL, or num_boundaries int64 positions within the row -- boundary j of a row is
  * then row[sorter[j]] (an entry outside [0, boundary_row_len) reads the row's last element).  The rank map is applied as elements are
  * read; boundaries, queries and sorter are never written, nor are bytes of `out` past num_queries entries.
- * num_queries == 0: VRS_OK, nothing done.  num_boundaries == 0: every output 0.  A NULL context, queries or out (boundaries, when
- * there are any), an unknown dtype or flag bit, element counts that are not whole rows, row counts that neither match nor equal one
+ * num_queries == 0: VRS_OK, nothing done.  num_boundaries == 0: every output 0.  A NULL context or out (boundaries, when
+ * there are any; queries on a NULL context -- on a valid one NULL queries are the identity queries below), an unknown dtype or flag bit, element counts that are not whole rows, row counts that neither match nor equal one
  * and undersized buffers: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Both element counts are below 2^32.
  * Tiers (vrs_search_tier, decided by vrs_search_tier_for from the shape and three thresholds): a row whose ranks fit
  * VRS_TUNE_SEARCH_LDS_BYTES is staged in LDS by every workgroup and searched there; 1- and 2-byte dtypes with one boundary row and
@@ -289,6 +289,18 @@ int vrs_quantile_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_
  * scratch: at least the bytes vrs_search_plan (or vrs_search_scratch_bytes for the tier) reports, may be NULL when that is 0 (the LDS
  * and direct tiers); contents on entry unspecified, afterwards unspecified.  Stream-ordered on the context's stream; the call only
  * enqueues (after settling a pending one-call sort) and never waits for the device.
+ * Identity queries (run-length decode; torch.repeat_interleave): queries == NULL with num_queries > 0 on a valid context means that
+ * query row i holds the values 0, 1, ..., query_row_len - 1 as integers of `dtype`, every row starting again at 0, also when all rows
+ * search the one boundary row.  The result is by definition what the same call writes when those queries are materialised, with
+ * VRS_SEARCH_RIGHT, VRS_SEARCH_OUT_INT64 and one boundary row or one per query row as above; with the boundaries the ends of runs
+ * (a cumulative sum of counts) and VRS_SEARCH_RIGHT, out[j] is the run of element j.  It is computed as a merge, not a search: per
+ * 4096 outputs the two ends are found by a few rounds of evenly spaced probes, the boundaries between them are read once and the
+ * outputs written once.  dtype is VRS_SORT_INT32 or VRS_SORT_INT64; any other dtype, VRS_SORT_INT32 with query_row_len above 2^31
+ * (its queries would pass 2^31 - 1) and a sorter other than NULL: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  scratch may
+ * be NULL: the form needs none.  num_boundaries == 0 gives zeros and num_queries == 0 returns VRS_OK as above; boundaries that are not
+ * ascending give some value in [0, boundary_row_len] per output, and nothing outside out's num_queries entries is written.  The form
+ * runs in no tier: it adds to none of the counters of vrs_search_stats, and vrs_search_plan, vrs_search_tier_for and
+ * vrs_search_scratch_bytes, which take no queries, cannot express it -- their answers are those of the materialised call.
  */
 enum { VRS_SEARCH_RIGHT = 1, VRS_SEARCH_OUT_INT64 = 2 }; /* flags */
 typedef enum vrs_search_tier {

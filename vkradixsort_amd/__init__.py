@@ -21,6 +21,9 @@ compact    torch.nonzero / argwhere / where(condition) / count_nonzero / masked_
            in three phases that wait nowhere -- count, carries, emit (nonzero, argwhere, where, count_nonzero, masked_select,
            masked_scatter); and x[mask] / index_put with a mask over the leading dims, every flag a whole row (mask_index,
            mask_index_put)
+repeat     torch.repeat_interleave drop-in: run-length decode, the undo of unique_consecutive(return_counts=True) -- cumsum, then the
+           identity form of the sorted search (a merge: boundaries read once, indices written once), then index_select
+           (repeat_interleave)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
            for torch tensors)
 """
@@ -32,6 +35,7 @@ from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, 
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
 from .quantile import nanquantile, quantile, quantile_scratch_bytes, quantile_segments, quantile_stats  # noqa: F401
 from .reduce import index_add, index_reduce, reduce_stats, scatter_reduce, segment_reduce  # noqa: F401
+from .repeat import repeat_interleave  # noqa: F401
 from .scan import cummax, cummin, cumprod, cumsum, scan_stats  # noqa: F401
 from .search import bucketize, search_stats, searchsorted  # noqa: F401
 from .segmented import segmented_stats, sort_rows, sort_segments  # noqa: F401

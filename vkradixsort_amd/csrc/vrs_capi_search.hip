@@ -33,6 +33,41 @@ int check_shape(vrs_context ctx, uint32_t num_boundaries, uint32_t boundary_row_
     return VRS_OK;
 }
 
+// queries == NULL: query row i holds 0, 1, ..., query_row_len - 1 (the merge of vrs_search.hip).  Rows as the caller gave them: with
+// one boundary row too, every query row starts again at 0.  No tier, no scratch, no counter of vrs_search_stats.
+int search_identity(vrs_context ctx, vrs_buffer boundaries, uint32_t num_boundaries, const Shape &s, uint32_t num_queries,
+                    uint32_t query_row_len, int dtype, int flags, vrs_buffer sorter, vrs_buffer out) {
+    int rc;
+    if (dtype != vrs::kSortI32 && dtype != vrs::kSortI64)
+        return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: queries == NULL (the identity queries) takes VRS_SORT_INT32 or VRS_SORT_INT64");
+    if (dtype == vrs::kSortI32 && query_row_len > (1u << 31))
+        return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: identity queries of VRS_SORT_INT32 end at 2^31 - 1 (query_row_len above 2^31)");
+    if (sorter) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: queries == NULL (the identity queries) takes no sorter");
+    if (!out || (num_boundaries != 0u && !boundaries)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
+    const size_t eb = static_cast<size_t>(vrs::sort_dtype_bytes(dtype)), ob = (flags & vrs::kSearchOutInt64) ? 8u : 4u;
+    if ((rc = check_buffer(ctx, out, num_queries * ob, "out")) ||
+        (num_boundaries != 0u && (rc = check_buffer(ctx, boundaries, num_boundaries * eb, "boundaries"))))
+        return rc;
+    VRS_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = settle_pending(ctx))) return rc;
+    if (s.m == 0u) {  // no boundary is below anything
+        VRS_HIP(ctx, hipMemsetAsync(out->ptr, 0, num_queries * ob, ctx->stream));
+        return VRS_OK;
+    }
+    vrs::SearchIdentityArgs a{};
+    a.boundaries = boundaries->ptr;
+    a.out = out->ptr;
+    a.m = s.m;
+    a.b_rows = s.b_rows;
+    a.q_rows = num_queries / query_row_len;
+    a.q_len = query_row_len;
+    a.right = (flags & vrs::kSearchRight) ? 1 : 0;
+    a.out64 = (flags & vrs::kSearchOutInt64) ? 1 : 0;
+    a.vec_ok = reinterpret_cast<uintptr_t>(a.out) % 16u == 0u && (a.q_rows == 1u || query_row_len % vrs::kSearchItems == 0u);
+    VRS_HIP(ctx, vrs::launch_search_identity(ctx->stream, a, dtype));
+    return VRS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -87,7 +122,8 @@ int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_bound
     if (flags & ~kKnownFlags) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: unknown flag bits");
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
     if (num_queries == 0u) return VRS_OK;
-    if (!queries || !out || (num_boundaries != 0u && !boundaries)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
+    if (!queries) return search_identity(ctx, boundaries, num_boundaries, s, num_queries, query_row_len, dtype, flags, sorter, out);
+    if (!out || (num_boundaries != 0u && !boundaries)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
     const size_t eb = static_cast<size_t>(vrs::sort_dtype_bytes(dtype)), ob = (flags & vrs::kSearchOutInt64) ? 8u : 4u;
     const int tier = vrs::search_tier(s.m, s.b_rows, s.q_per_row, dtype, ctx->search_lds_bytes, ctx->search_table_min_queries,
                                       ctx->search_index_min_queries);

@@ -11,6 +11,8 @@
 // Every search is the same branch-free loop over a fixed length (the row's, the stride, the line), so a wave never diverges; a probe
 // past the end of a window's valid part counts as "not below", which also keeps unsorted input inside [0, m] and inside the buffers.
 // Positions: base + half never exceeds the window's length, windows start at multiples of the line below m < 2^32.
+// Identity queries (queries == NULL: 0, 1, 2, ... per row) take none of the four: search_identity_kernel merges, one chunk of
+// kSearchChunk outputs per workgroup -- two ends by wave-wide probes, the boundaries between them counted into LDS, one prefix sum.
 #include "vrs_search.hpp"
 
 namespace vrs {
@@ -275,7 +277,105 @@ hipError_t search_as(hipStream_t stream, SearchArgs a, int tier, const SearchLay
     }
 }
 
+// ---- identity queries: the merge (vrs_search.hpp has the chunk's marking and scan)
+
+constexpr uint32_t kSearchWaves = kSearchThreads / 64u;
+static_assert(kSearchThreads * kSearchItems == kSearchChunk, "every lane of the identity kernel scans one group of a chunk");
+
+// How many of the row's m ascending boundaries are below v (right: or equal), found by one wave: 64 evenly spaced probes and a ballot
+// per round leave 1/65 of the window, so 2^32 boundaries take six dependent rounds instead of 32.  Wave-uniform result.  Every probe
+// is inside the window, and the window inside the row, whatever the boundaries hold: a result in [0, m].
+template <typename S>
+__device__ inline uint32_t wave_count_below(const S *row, uint32_t m, int64_t v, int right) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t lo = 0u, len = m;  // the result is in [lo, lo + len]
+    while (len != 0u) {
+        const uint32_t step = len / 65u + 1u;          // (64 * step > len - step: what the probes leave is shorter than step)
+        const uint32_t idx = (lane + 1u) * step - 1u;  // (< 2^32: step <= 2^32 / 65 + 1)
+        const bool hit = idx < len && below<int64_t>(static_cast<int64_t>(row[lo + idx]), v, right);
+        const uint32_t c = static_cast<uint32_t>(__popcll(__ballot(hit)));  // (c probes are inside the window: c * step <= len)
+        lo += c * step;
+        len = min(step - 1u, len - c * step);
+    }
+    return lo;
+}
+
+// the workgroup as a team of search_identity_chunk
+struct SearchIdentityTeam {
+    uint32_t *wave_sums;  // kSearchWaves words of LDS
+    __device__ void barrier() { __syncthreads(); }
+    __device__ void add(uint32_t *slot) { atomicAdd(slot, 1u); }
+    __device__ uint32_t exclusive(uint32_t x) {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        uint32_t incl = x;
+#pragma unroll
+        for (uint32_t d = 1u; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63u) wave_sums[wave] = incl;
+        __syncthreads();
+        uint32_t before = incl - x;
+        for (uint32_t w = 0; w < wave; ++w) before += wave_sums[w];
+        return before;
+    }
+};
+
+template <typename S, typename O>
+__global__ __launch_bounds__(kSearchThreads) void search_identity_kernel(SearchIdentityArgs a) {
+    __shared__ __align__(16) uint32_t marks[kSearchChunk];
+    __shared__ uint32_t wave_sums[kSearchWaves];
+    __shared__ uint32_t ends[2];
+    const uint64_t j0 = static_cast<uint64_t>(blockIdx.x) * kSearchChunk;
+    const uint32_t n = static_cast<uint32_t>(min(a.q_len - j0, static_cast<uint64_t>(kSearchChunk)));
+    SearchIdentityTeam team{wave_sums};
+    for (uint64_t q_row = blockIdx.y; q_row < a.q_rows; q_row += gridDim.y) {  // (64-bit: q_row + gridDim.y may pass 2^32)
+        const S *row = static_cast<const S *>(a.boundaries) + (a.b_rows == 1u ? 0u : static_cast<size_t>(q_row) * a.m);
+        // waves 0 and 1 find the two ends: the answers of the chunk's first and last output
+        if (threadIdx.x < 128u) {
+            const uint32_t which = threadIdx.x >> 6;
+            const uint32_t e = wave_count_below<S>(row, a.m, static_cast<int64_t>(j0 + (which ? n - 1u : 0u)), a.right);
+            if ((threadIdx.x & 63u) == 0u) ends[which] = e;
+        }
+        O *out = static_cast<O *>(a.out) + static_cast<size_t>(q_row) * a.q_len + j0;
+        const int vec_ok = a.vec_ok;
+        __syncthreads();
+        const uint32_t a0 = ends[0], a1 = ends[1];
+        search_identity_chunk<S>(row, a0, a1, j0, n, a.right, marks, threadIdx.x, kSearchThreads, team,
+                                 [&](uint32_t g, const uint32_t (&v)[kSearchItems], uint32_t k) {
+                                     if (vec_ok && k == kSearchItems) {
+                                         Quad<O, 16> o;
+#pragma unroll
+                                         for (uint32_t i = 0; i < kSearchItems; ++i) o.v[i] = static_cast<O>(v[i]);
+                                         *reinterpret_cast<Quad<O, 16> *>(out + g) = o;
+                                     } else {
+                                         for (uint32_t i = 0; i < k; ++i) out[g + i] = static_cast<O>(v[i]);
+                                     }
+                                 });
+        __syncthreads();  // (the next row's searches write `ends`, its chunk clears the marks)
+    }
+}
+
+template <typename S>
+hipError_t identity_as(hipStream_t stream, const SearchIdentityArgs &a) {
+    const uint64_t chunks = (a.q_len + kSearchChunk - 1u) / kSearchChunk;  // (2^20 at most)
+    const dim3 grid(static_cast<uint32_t>(chunks), std::min<uint32_t>(a.q_rows, 65535u));
+    if (a.out64)
+        hipLaunchKernelGGL((search_identity_kernel<S, int64_t>), grid, dim3(kSearchThreads), 0, stream, a);
+    else
+        hipLaunchKernelGGL((search_identity_kernel<S, uint32_t>), grid, dim3(kSearchThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_search_identity(hipStream_t stream, const SearchIdentityArgs &a, int dtype) {
+    switch (dtype) {
+        case kSortI32: return identity_as<int32_t>(stream, a);
+        case kSortI64: return identity_as<int64_t>(stream, a);
+        default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_search(hipStream_t stream, SearchArgs a, int dtype, int tier, uint32_t lds_bytes, const SearchLayout &L, char *scratch) {
     a.shape = search_index_shape(a.m, dtype, lds_bytes);

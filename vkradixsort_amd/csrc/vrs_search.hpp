@@ -1,6 +1,6 @@
 // vrs_search.hpp -- what the sorted-sequence search's kernels (vrs_search.hip) and their host side (vrs_capi_search.hip) share: the tiers
 // and the function that picks one (exported as vrs_search_tier_for), the shape of the sampled index, the scratch layout and the launch
-// wrapper.  Internal.
+// wrapper; and the identity form's chunk function (search_identity_chunk), which the merge kernel and a host program both run.  Internal.
 #pragma once
 #include <algorithm>
 
@@ -100,5 +100,75 @@ struct SearchArgs {
 
 // the launches of one call in `tier` (the table / index build included)
 hipError_t launch_search(hipStream_t stream, SearchArgs a, int dtype, int tier, uint32_t lds_bytes, const SearchLayout &L, char *scratch);
+
+// ---- Identity queries (vrs_search_sorted with queries == NULL: query row i holds 0, 1, ..., q_len - 1): a merge, not a search.
+// One work item is a chunk of kSearchChunk consecutive outputs [j0, j0 + n) of a row.  With a0 = the answer for j0 and a1 = the answer
+// for the chunk's last output, the boundaries [a0, a1) of the row are exactly those that change the answer inside the chunk: boundary b
+// raises it by one from output b on (right: b <= j) or from output b + 1 on (left: b < j).  So every such boundary adds one to a counter
+// at its output's place in the chunk, and the answers are a0 + the inclusive prefix sums of those counters.
+
+// The place in the chunk [j0, j0 + n) from which boundary b counts, or n when it is outside (ascending boundaries within [a0, a1) never
+// are; ones that are not ascending may be anywhere).  lo = j0 - 1 >= -1 and b >= lo, so the difference is exact in uint64.
+__host__ __device__ inline uint32_t search_identity_place(int64_t b, uint64_t j0, uint32_t n, int right) {
+    const int64_t lo = static_cast<int64_t>(j0) - (right ? 0 : 1);
+    if (b < lo) return n;
+    const uint64_t p = static_cast<uint64_t>(b) - static_cast<uint64_t>(lo);
+    return p < n ? static_cast<uint32_t>(p) : n;
+}
+
+// The marking and the scan of one chunk over plain arrays, written for a team of `threads` lanes of which this is lane `tid`.  The
+// kernel runs it with kSearchThreads lanes, marks in LDS and a Team whose add() is an LDS atomic, whose barrier() is the workgroup's and
+// whose exclusive() is a workgroup scan; a host program runs the same code with one lane (SearchIdentitySerial).
+//   row    the boundary row (S = int32_t or int64_t); entries [a0, a1) are read, in pieces of kSearchChunk however many there are
+//   marks  kSearchChunk words, contents on entry unspecified
+//   store  store(g, v, k): outputs g .. g + k - 1 of the chunk (g a multiple of kSearchItems, k <= kSearchItems) are v[0 .. k - 1]
+// Team::exclusive(x) returns the sum of the x of every earlier call in lane order (lane 0's first call, lane 1's first call, ...);
+// every lane of a workgroup team calls it exactly once, which static_asserts in the kernel hold to kSearchThreads * kSearchItems ==
+// kSearchChunk.  Every answer lies in [a0, max(a0, a1)] whatever the boundaries hold.
+template <typename S, typename Team, typename Store>
+__host__ __device__ inline void search_identity_chunk(const S *row, uint32_t a0, uint32_t a1, uint64_t j0, uint32_t n, int right,
+                                                      uint32_t *marks, uint32_t tid, uint32_t threads, Team &team, Store store) {
+    for (uint32_t g = tid; g < kSearchChunk; g += threads) marks[g] = 0u;
+    team.barrier();
+    for (uint64_t base = a0; base < a1; base += kSearchChunk) {  // (64-bit: base + kSearchChunk may pass 2^32)
+        const uint64_t end = base + kSearchChunk < a1 ? base + kSearchChunk : a1;
+        for (uint64_t i = base + tid; i < end; i += threads) {
+            const uint32_t p = search_identity_place(static_cast<int64_t>(row[i]), j0, n, right);
+            if (p < n) team.add(marks + p);
+        }
+    }
+    team.barrier();
+    for (uint32_t g = tid * kSearchItems; g < kSearchChunk; g += threads * kSearchItems) {
+        uint32_t v[kSearchItems];
+        uint32_t sum = 0u;
+        for (uint32_t k = 0; k < kSearchItems; ++k) v[k] = sum += marks[g + k];
+        const uint32_t before = a0 + team.exclusive(sum);
+        for (uint32_t k = 0; k < kSearchItems; ++k) v[k] += before;
+        if (g < n) store(g, v, n - g < kSearchItems ? n - g : kSearchItems);
+    }
+}
+
+// the team of one: what a host program (or a single device lane) passes
+struct SearchIdentitySerial {
+    uint32_t running = 0u;
+    __host__ __device__ void barrier() {}
+    __host__ __device__ void add(uint32_t *slot) { *slot += 1u; }
+    __host__ __device__ uint32_t exclusive(uint32_t x) {
+        const uint32_t r = running;
+        running += x;
+        return r;
+    }
+};
+
+struct SearchIdentityArgs {
+    const void *boundaries;  // b_rows rows of m elements of int32 / int64
+    void *out;               // q_rows x q_len uint32 / int64
+    uint32_t m, b_rows, q_rows;
+    uint64_t q_len;          // outputs per row (below 2^32)
+    int right, out64, vec_ok;  // vec_ok: every group of four outputs may move as aligned 16-byte vectors
+};
+
+// the one launch of an identity call (dtype: kSortI32 or kSortI64; m, q_rows and q_len all nonzero)
+hipError_t launch_search_identity(hipStream_t stream, const SearchIdentityArgs &a, int dtype);
 
 }  // namespace vrs

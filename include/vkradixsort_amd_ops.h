@@ -301,8 +301,22 @@ int vrs_quantile_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_
  * ascending give some value in [0, boundary_row_len] per output, and nothing outside out's num_queries entries is written.  The form
  * runs in no tier: it adds to none of the counters of vrs_search_stats, and vrs_search_plan, vrs_search_tier_for and
  * vrs_search_scratch_bytes, which take no queries, cannot express it -- their answers are those of the materialised call.
+ * Membership (torch.isin / numpy.isin): with VRS_SEARCH_MEMBER `out` is ONE BYTE per query,
+ *     out[q] = 1 when some boundary b of the query's row has r(b) == r(queries[q]) and queries[q] is not a NaN, 0 otherwise,
+ * and with VRS_SEARCH_MEMBER_INVERT as well the two values are swapped.  So -0.0 is a member of a row that holds +0.0 (and the reverse),
+ * and a NaN is a member of nothing, even of a row that holds NaNs: IEEE ==, numpy.isin's answer and torch.isin's.  Everything else is
+ * the counting call's: the rank map applied as elements are read, the sorter, one boundary row or one per query row, the tier (the one
+ * vrs_search_plan reports: these take no flags), its scratch (the table keeps its 4-byte entries and holds 0 / 1 in them) and its
+ * counter of vrs_search_stats; stream-ordered, enqueue-only, never waits.  Nothing but out's num_queries bytes is written.
+ * num_queries == 0: VRS_OK.  num_boundaries == 0: every output 0 (inverted: 1).  Boundaries that are not ascending: 0 or 1 per query,
+ * no fault.  The left count c of a query is found as above, then boundary c is fetched once -- never when c == boundary_row_len.
+ * VRS_SEARCH_MEMBER with VRS_SEARCH_RIGHT or VRS_SEARCH_OUT_INT64, VRS_SEARCH_MEMBER_INVERT without VRS_SEARCH_MEMBER,
+ * VRS_SEARCH_MEMBER with queries == NULL (the identity queries) and an out of fewer than num_queries bytes:
+ * VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
  */
-enum { VRS_SEARCH_RIGHT = 1, VRS_SEARCH_OUT_INT64 = 2 }; /* flags */
+enum { VRS_SEARCH_RIGHT = 1, VRS_SEARCH_OUT_INT64 = 2, /* flags; bits 4 and 8 are none: they stay unknown flag bits and are refused */
+       VRS_SEARCH_MEMBER = 16,       /* out: one byte per query, 1 = the query equals some boundary of its row */
+       VRS_SEARCH_MEMBER_INVERT = 32 /* with VRS_SEARCH_MEMBER only: 0 = the query equals some boundary of its row */ };
 typedef enum vrs_search_tier {
     VRS_SEARCH_LDS = 0,    /* the row's ranks fit VRS_TUNE_SEARCH_LDS_BYTES (no boundaries at all included) */
     VRS_SEARCH_TABLE = 1,  /* 1- / 2-byte dtype, one boundary row, VRS_TUNE_SEARCH_TABLE_MIN_QUERIES queries or more (1-byte: 1/256 of it) */

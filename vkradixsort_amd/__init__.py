@@ -10,7 +10,8 @@ selection  torch.kthvalue / torch.median / torch.nanmedian drop-ins by a one-ran
 quantile   torch.quantile / torch.nanquantile drop-ins by a multi-rank radix select: up to 16 order statistics per row carried through one
            sequence of reads, values only (quantile_segments over Buffers; quantile, nanquantile for torch tensors)
 sort       torch.sort / torch.argsort drop-ins: any dim, descending, nine dtypes, torch's order bit for bit (sort, sort_values, argsort)
-search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize)
+search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize);
+           torch.isin by a sort of the test set and the search's membership form, a byte per element (isin)
 binning    torch.bincount / torch.histc / torch.histogram drop-ins: counters in LDS or global memory, integer counts converted once
            (bincount, histc, histogram)
 reduce     torch.segment_reduce / index_add / index_reduce / scatter_reduce drop-ins with reproducible sums: a segmented reduction over
@@ -37,7 +38,7 @@ from .quantile import nanquantile, quantile, quantile_scratch_bytes, quantile_se
 from .reduce import index_add, index_reduce, reduce_stats, scatter_reduce, segment_reduce  # noqa: F401
 from .repeat import repeat_interleave  # noqa: F401
 from .scan import cummax, cummin, cumprod, cumsum, scan_stats  # noqa: F401
-from .search import bucketize, search_stats, searchsorted  # noqa: F401
+from .search import bucketize, isin, search_stats, searchsorted  # noqa: F401
 from .segmented import segmented_stats, sort_rows, sort_segments  # noqa: F401
 from .selection import kthvalue, median, nanmedian, select_scratch_bytes, select_segments, select_stats  # noqa: F401
 from .sort import argsort, sort, sort_values  # noqa: F401

@@ -109,6 +109,7 @@ RLE_TILE = 4096
 VRS_SORT_DESCENDING = 1
 # sorted-sequence search (vrs_search_sorted): flags, tiers (vrs_search_tier), tuning keys and the library's defaults for them
 VRS_SEARCH_RIGHT, VRS_SEARCH_OUT_INT64 = 1, 2
+VRS_SEARCH_MEMBER, VRS_SEARCH_MEMBER_INVERT = 16, 32  # the membership form (isin): a byte per query; bits 4 and 8 stay refused
 VRS_SEARCH_LDS, VRS_SEARCH_TABLE, VRS_SEARCH_DIRECT, VRS_SEARCH_INDEXED = 0, 1, 2, 3
 VRS_TUNE_SEARCH_LDS_BYTES, VRS_TUNE_SEARCH_TABLE_MIN_QUERIES, VRS_TUNE_SEARCH_INDEX_MIN_QUERIES = 29, 30, 31
 SEARCH_LDS_BYTES_DEFAULT, SEARCH_LDS_BYTES_MAX = 64 * 1024, 160 * 1024

@@ -1,5 +1,5 @@
 // vrs_capi_search.hip -- the C ABI of the sorted-sequence search (vrs_search_*): argument checks, the tier decision, the scratch layout
-// and the launches of vrs_search.hip.
+// and the launches of vrs_search.hip, in the counting form and the membership form (VRS_SEARCH_MEMBER: a byte per query).
 #include "vrs_host.hpp"
 #include "vrs_search.hpp"
 
@@ -7,7 +7,7 @@ using namespace vrsh;
 
 namespace {
 
-constexpr int kKnownFlags = vrs::kSearchRight | vrs::kSearchOutInt64;
+constexpr int kKnownFlags = vrs::kSearchRight | vrs::kSearchOutInt64 | vrs::kSearchMember | vrs::kSearchMemberInvert;  // (not bits 4 and 8)
 
 struct Shape {
     uint32_t m, b_rows, q_rows, q_len, q_per_row;  // q_rows x q_len as the kernels walk them; q_per_row: queries per boundary row
@@ -120,11 +120,19 @@ int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_bound
     int rc;
     if ((rc = check_shape(ctx, num_boundaries, boundary_row_len, num_queries, query_row_len, dtype, &s))) return rc;
     if (flags & ~kKnownFlags) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: unknown flag bits");
+    const bool member = (flags & vrs::kSearchMember) != 0;
+    if ((flags & vrs::kSearchMemberInvert) && !member)
+        return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: VRS_SEARCH_MEMBER_INVERT is valid only together with VRS_SEARCH_MEMBER");
+    if (member && (flags & (vrs::kSearchRight | vrs::kSearchOutInt64)))
+        return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: VRS_SEARCH_MEMBER takes neither VRS_SEARCH_RIGHT nor VRS_SEARCH_OUT_INT64 (out is one byte per query)");
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
     if (num_queries == 0u) return VRS_OK;
+    if (!queries && member)
+        return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "search: VRS_SEARCH_MEMBER needs queries (queries == NULL, the identity queries, has no membership form)");
     if (!queries) return search_identity(ctx, boundaries, num_boundaries, s, num_queries, query_row_len, dtype, flags, sorter, out);
     if (!out || (num_boundaries != 0u && !boundaries)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
-    const size_t eb = static_cast<size_t>(vrs::sort_dtype_bytes(dtype)), ob = (flags & vrs::kSearchOutInt64) ? 8u : 4u;
+    const int invert = (flags & vrs::kSearchMemberInvert) ? 1 : 0;
+    const size_t eb = static_cast<size_t>(vrs::sort_dtype_bytes(dtype)), ob = member ? 1u : (flags & vrs::kSearchOutInt64) ? 8u : 4u;
     const int tier = vrs::search_tier(s.m, s.b_rows, s.q_per_row, dtype, ctx->search_lds_bytes, ctx->search_table_min_queries,
                                       ctx->search_index_min_queries);
     const vrs::SearchLayout L = vrs::search_layout(s.m, s.b_rows, dtype, sorter != nullptr, tier);
@@ -138,8 +146,8 @@ int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_bound
     }
     VRS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = settle_pending(ctx))) return rc;
-    if (s.m == 0u) {  // no boundary is below anything
-        VRS_HIP(ctx, hipMemsetAsync(out->ptr, 0, num_queries * ob, ctx->stream));
+    if (s.m == 0u) {  // no boundary is below anything, nothing is a member (inverted: every byte 1)
+        VRS_HIP(ctx, hipMemsetAsync(out->ptr, invert, num_queries * ob, ctx->stream));
         return VRS_OK;
     }
     vrs::SearchArgs a{};
@@ -153,8 +161,11 @@ int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_bound
     a.q_len = s.q_len;
     a.right = (flags & vrs::kSearchRight) ? 1 : 0;
     a.out64 = (flags & vrs::kSearchOutInt64) ? 1 : 0;
-    const size_t q_align = std::min<size_t>(eb * vrs::kSearchItems, 16u);
-    a.vec_ok = reinterpret_cast<uintptr_t>(a.queries) % q_align == 0u && reinterpret_cast<uintptr_t>(a.out) % 16u == 0u &&
+    a.member = member ? 1 : 0;
+    a.invert = invert;
+    // four answers move as one vector: 16 bytes of uint32, 32 of int64 (16-byte aligned halves), one 4-byte word of membership bytes
+    const size_t q_align = std::min<size_t>(eb * vrs::kSearchItems, 16u), o_align = member ? 4u : 16u;
+    a.vec_ok = reinterpret_cast<uintptr_t>(a.queries) % q_align == 0u && reinterpret_cast<uintptr_t>(a.out) % o_align == 0u &&
                (s.q_rows == 1u || s.q_len % vrs::kSearchItems == 0u);
     // work items: every chunk of a query row; with a boundary row per query row a workgroup stages that row for each of its items,
     // so a long row is cut into fewer, longer chunks (about 2048 items per call)

@@ -13,6 +13,9 @@
 // Positions: base + half never exceeds the window's length, windows start at multiples of the line below m < 2^32.
 // Identity queries (queries == NULL: 0, 1, 2, ... per row) take none of the four: search_identity_kernel merges, one chunk of
 // kSearchChunk outputs per workgroup -- two ends by wave-wide probes, the boundaries between them counted into LDS, one prefix sum.
+// Membership (VRS_SEARCH_MEMBER: torch.isin) is a template parameter of the query and table kernels: the left count by the same code,
+// then one fetch of the boundary at the count -- guarded, count == m is one past the row -- search_member (vrs_search.hpp) and a byte
+// per query, four of them as one word where the address allows it.
 #include "vrs_search.hpp"
 
 namespace vrs {
@@ -24,6 +27,7 @@ struct SearchTraits {
     using R = R_;
     static constexpr int B = 8 * static_cast<int>(sizeof(S_));
     __device__ static R rank(S u, R inf_bits) { return sort_rank<R, B, FLOAT_, SIGNED_>(static_cast<R>(u), inf_bits, false); }
+    __device__ static bool is_nan(R r) { return search_rank_is_nan<R, B, FLOAT_>(r); }
 };
 
 template <typename E, int A>
@@ -63,10 +67,12 @@ __device__ inline typename T::R boundary_rank(const typename T::S *row, const in
 
 constexpr int kModeLds = 0, kModeTable = 1, kModeDirect = 2, kModeIndexed = 3;
 
-template <typename T, int MODE>
+// MEMBER (VRS_SEARCH_MEMBER): the left count as before, then one guarded fetch of the boundary at the count and a byte per query.
+template <typename T, int MODE, bool MEMBER>
 __global__ __launch_bounds__(kSearchThreads) void search_kernel(SearchArgs a) {
     using S = typename T::S;
     using R = typename T::R;
+    const int right = MEMBER ? 0 : a.right;
     extern __shared__ __align__(16) unsigned char search_smem[];
     R *lds = reinterpret_cast<R *>(search_smem);
     const R inf_bits = static_cast<R>(a.inf_bits);
@@ -111,39 +117,70 @@ __global__ __launch_bounds__(kSearchThreads) void search_kernel(SearchArgs a) {
                 R v[kSearchItems];
 #pragma unroll
                 for (uint32_t k = 0; k < kSearchItems; ++k) v[k] = T::rank(q[k], inf_bits);
+                const R *gathered = nullptr;
                 if (MODE == kModeLds) {
-                    search_window<R>(a.m, v, a.right, [&](uint32_t i, uint32_t, R x) { return below(lds[i], x, a.right); }, count);
+                    search_window<R>(a.m, v, right, [&](uint32_t i, uint32_t, R x) { return below(lds[i], x, right); }, count);
                 } else if (MODE == kModeDirect) {
-                    search_window<R>(a.m, v, a.right,
-                                     [&](uint32_t i, uint32_t, R x) { return below(boundary_rank<T>(row, sorter, a.m, i, inf_bits), x, a.right); }, count);
+                    search_window<R>(a.m, v, right,
+                                     [&](uint32_t i, uint32_t, R x) { return below(boundary_rank<T>(row, sorter, a.m, i, inf_bits), x, right); }, count);
                 } else {
                     const SearchIndexShape sh = a.shape;
                     const R *index = static_cast<const R *>(a.index) + static_cast<size_t>(b_row) * sh.full;
-                    const R *gathered = a.gathered ? static_cast<const R *>(a.gathered) + static_cast<size_t>(b_row) * a.m : nullptr;
+                    gathered = a.gathered ? static_cast<const R *>(a.gathered) + static_cast<size_t>(b_row) * a.m : nullptr;
                     uint32_t c0[kSearchItems], c1[kSearchItems];
-                    search_window<R>(sh.top, v, a.right, [&](uint32_t i, uint32_t, R x) { return below(lds[i], x, a.right); }, c0);
-                    search_window<R>(sh.stride, v, a.right,
+                    search_window<R>(sh.top, v, right, [&](uint32_t i, uint32_t, R x) { return below(lds[i], x, right); }, c0);
+                    search_window<R>(sh.stride, v, right,
                                      [&](uint32_t i, uint32_t k, R x) {
                                          const uint32_t at = c0[k] * sh.stride + i;  // (c0 * stride <= full <= 2^28 and i < stride <= max(full, 32))
-                                         return at < sh.full && below(index[at], x, a.right);
+                                         return at < sh.full && below(index[at], x, right);
                                      },
                                      c1);
                     uint32_t lines[kSearchItems];
 #pragma unroll
                     for (uint32_t k = 0; k < kSearchItems; ++k) lines[k] = c0[k] * sh.stride + c1[k];  // <= full
-                    search_window<R>(sh.line, v, a.right,
+                    search_window<R>(sh.line, v, right,
                                      [&](uint32_t i, uint32_t k, R x) {
                                          const uint64_t at = static_cast<uint64_t>(lines[k]) * sh.line + i;
                                          if (at >= a.m) return false;
                                          const uint32_t j = static_cast<uint32_t>(at);
-                                         return below(gathered ? gathered[j] : T::rank(row[j], inf_bits), x, a.right);
+                                         return below(gathered ? gathered[j] : T::rank(row[j], inf_bits), x, right);
                                      },
                                      count);
 #pragma unroll
                     for (uint32_t k = 0; k < kSearchItems; ++k) count[k] += lines[k] * sh.line;  // <= m
                 }
+                if (MEMBER) {
+                    // boundary count[k] decides, fetched only where it exists: a query above every boundary has count == m, one
+                    // past the row (and past the staged ranks).  Lanes past the chunk's end hold S{} queries and are not stored.
+#pragma unroll
+                    for (uint32_t k = 0; k < kSearchItems; ++k) {
+                        const uint32_t c = count[k];
+                        R e = R{};
+                        if (c < a.m) {
+                            if (MODE == kModeLds) e = lds[c];
+                            else if (MODE == kModeDirect) e = boundary_rank<T>(row, sorter, a.m, c, inf_bits);
+                            else e = gathered ? gathered[c] : T::rank(row[c], inf_bits);
+                        }
+                        count[k] = search_member<R>(c, a.m, e, v[k], T::is_nan(v[k]));
+                    }
+                }
             }
-            if (a.out64) {
+            if (MEMBER) {
+                // (the table tier's entries are the membership itself.)  Four answers as one word when the chunk is whole and the
+                // address allows it (vec_ok: out 4-byte aligned, rows a multiple of four), else byte by byte.
+                const uint32_t flip = a.invert ? 1u : 0u;
+                unsigned char *out = static_cast<unsigned char *>(a.out) + origin + g;
+                if (whole) {
+                    uint32_t word = 0u;
+#pragma unroll
+                    for (uint32_t k = 0; k < kSearchItems; ++k) word |= (count[k] ^ flip) << (8u * k);
+                    *reinterpret_cast<uint32_t *>(out) = word;
+                } else {
+#pragma unroll
+                    for (uint32_t k = 0; k < kSearchItems; ++k)
+                        if (g + k < len) out[k] = static_cast<unsigned char>(count[k] ^ flip);
+                }
+            } else if (a.out64) {
                 int64_t *out = static_cast<int64_t *>(a.out) + origin + g;
                 if (whole) {
                     Quad<int64_t, 16> o;
@@ -172,8 +209,9 @@ __global__ __launch_bounds__(kSearchThreads) void search_kernel(SearchArgs a) {
     }
 }
 
-// table[u] = the answer for a query of bit pattern u: one direct search per pattern (one shared boundary row)
-template <typename T>
+// table[u] = the answer for a query of bit pattern u: one direct search per pattern (one shared boundary row).  MEMBER: the left count,
+// then whether the pattern is a member (0 / 1 in the same 4-byte entries; the query kernel inverts).
+template <typename T, bool MEMBER>
 __global__ __launch_bounds__(256) void search_table_kernel(SearchArgs a, uint32_t *__restrict__ table) {
     using S = typename T::S;
     using R = typename T::R;
@@ -181,13 +219,18 @@ __global__ __launch_bounds__(256) void search_table_kernel(SearchArgs a, uint32_
     const R inf_bits = static_cast<R>(a.inf_bits);
     const S *row = static_cast<const S *>(a.boundaries);
     const R v = T::rank(static_cast<S>(u), inf_bits);
+    const int right = MEMBER ? 0 : a.right;
     uint32_t base = 0u, len = a.m;
     while (len > 1u) {
         const uint32_t half = len >> 1;
-        base += below(boundary_rank<T>(row, a.sorter, a.m, base + half - 1u, inf_bits), v, a.right) ? half : 0u;
+        base += below(boundary_rank<T>(row, a.sorter, a.m, base + half - 1u, inf_bits), v, right) ? half : 0u;
         len -= half;
     }
-    if (a.m != 0u) base += below(boundary_rank<T>(row, a.sorter, a.m, base, inf_bits), v, a.right) ? 1u : 0u;
+    if (a.m != 0u) base += below(boundary_rank<T>(row, a.sorter, a.m, base, inf_bits), v, right) ? 1u : 0u;
+    if (MEMBER) {
+        const R e = base < a.m ? boundary_rank<T>(row, a.sorter, a.m, base, inf_bits) : R{};  // (boundary m does not exist)
+        base = search_member<R>(base, a.m, e, v, T::is_nan(v));
+    }
     table[u] = base;
 }
 
@@ -222,7 +265,7 @@ __global__ __launch_bounds__(256) void search_index_kernel(SearchArgs a, typenam
     }
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool MEMBER>
 hipError_t launch_query(hipStream_t stream, const SearchArgs &a, uint32_t lds_entries) {
     using R = typename T::R;
     const bool uses_lds = MODE == kModeLds || MODE == kModeIndexed;
@@ -231,7 +274,7 @@ hipError_t launch_query(hipStream_t stream, const SearchArgs &a, uint32_t lds_en
     // as many workgroups as stay resident: two of 1024 threads per CU, one when its LDS is more than half a CU's
     const uint32_t resident = 256u * (uses_lds && lds > kSearchLdsMaxBytes / 2u ? 1u : 2u);
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(items, uses_lds ? resident : 4u * resident));
-    auto kernel = search_kernel<T, MODE>;
+    auto kernel = search_kernel<T, MODE, MEMBER>;
     if (lds > 64u * 1024u) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         if (e != hipSuccess) return e;
@@ -240,21 +283,21 @@ hipError_t launch_query(hipStream_t stream, const SearchArgs &a, uint32_t lds_en
     return hipGetLastError();
 }
 
-template <typename T>
-hipError_t search_as(hipStream_t stream, SearchArgs a, int tier, const SearchLayout &L, char *scratch) {
+template <typename T, bool MEMBER>
+hipError_t search_form(hipStream_t stream, SearchArgs a, int tier, const SearchLayout &L, char *scratch) {
     using R = typename T::R;
     switch (tier) {
         case kSearchTierLds:
             a.stage_len = a.m;
-            return launch_query<T, kModeLds>(stream, a, a.m);
-        case kSearchTierDirect: return launch_query<T, kModeDirect>(stream, a, 0u);
+            return launch_query<T, kModeLds, MEMBER>(stream, a, a.m);
+        case kSearchTierDirect: return launch_query<T, kModeDirect, MEMBER>(stream, a, 0u);
         case kSearchTierTable:
             if constexpr (sizeof(typename T::S) <= 2) {
                 uint32_t *table = reinterpret_cast<uint32_t *>(scratch + L.table);
-                hipLaunchKernelGGL(search_table_kernel<T>, dim3((1u << T::B) / 256u), dim3(256), 0, stream, a, table);
+                hipLaunchKernelGGL((search_table_kernel<T, MEMBER>), dim3((1u << T::B) / 256u), dim3(256), 0, stream, a, table);
                 if (const hipError_t e = hipGetLastError()) return e;
                 a.table = table;
-                return launch_query<T, kModeTable>(stream, a, 0u);
+                return launch_query<T, kModeTable, MEMBER>(stream, a, 0u);
             } else {
                 return hipErrorInvalidValue;
             }
@@ -271,10 +314,16 @@ hipError_t search_as(hipStream_t stream, SearchArgs a, int tier, const SearchLay
             a.top = top;
             a.gathered = gathered;
             a.stage_len = a.shape.top;
-            return launch_query<T, kModeIndexed>(stream, a, a.shape.top);
+            return launch_query<T, kModeIndexed, MEMBER>(stream, a, a.shape.top);
         }
         default: return hipErrorInvalidValue;
     }
+}
+
+// the form is a template parameter: the counting kernels are the instantiations they were
+template <typename T>
+hipError_t search_as(hipStream_t stream, const SearchArgs &a, int tier, const SearchLayout &L, char *scratch) {
+    return a.member ? search_form<T, true>(stream, a, tier, L, scratch) : search_form<T, false>(stream, a, tier, L, scratch);
 }
 
 // ---- identity queries: the merge (vrs_search.hpp has the chunk's marking and scan)

@@ -1,6 +1,7 @@
 // vrs_search.hpp -- what the sorted-sequence search's kernels (vrs_search.hip) and their host side (vrs_capi_search.hip) share: the tiers
 // and the function that picks one (exported as vrs_search_tier_for), the shape of the sampled index, the scratch layout and the launch
-// wrapper; and the identity form's chunk function (search_identity_chunk), which the merge kernel and a host program both run.  Internal.
+// wrapper; the identity form's chunk function (search_identity_chunk), which the merge kernel and a host program both run; and the
+// membership form's decision (search_member), which every query mode, the table kernel and a host program run.  Internal.
 #pragma once
 #include <algorithm>
 
@@ -10,6 +11,7 @@ namespace vrs {
 
 constexpr int kSearchTierLds = 0, kSearchTierTable = 1, kSearchTierDirect = 2, kSearchTierIndexed = 3, kSearchTiers = 4;
 constexpr int kSearchRight = 1, kSearchOutInt64 = 2;  // VRS_SEARCH_RIGHT, VRS_SEARCH_OUT_INT64
+constexpr int kSearchMember = 16, kSearchMemberInvert = 32;  // VRS_SEARCH_MEMBER, VRS_SEARCH_MEMBER_INVERT (bits 4 and 8: unknown, refused)
 constexpr uint32_t kSearchThreads = 1024u, kSearchItems = 4u, kSearchChunk = kSearchThreads * kSearchItems;  // queries per workgroup pass
 constexpr uint32_t kSearchLine = 128u;  // bytes of boundaries one index entry stands for: what a query's last global fetch brings in
 // The measured settings (DESIGN "K10", profiles/labs/k10_searchsorted.txt):
@@ -82,13 +84,31 @@ inline SearchLayout search_layout(uint32_t m, uint32_t b_rows, int dtype, bool s
     return L;
 }
 
+// ---- Membership (VRS_SEARCH_MEMBER: torch.isin / numpy.isin).  The decision, written once for the four query modes, the table kernel
+// and a host program: with c = the left count of a query of rank v among the m boundaries of its row (c <= m, boundaries ascending),
+// the query is a member exactly when boundary c exists and has the query's rank -- unless the query is of the NaN class, which IEEE ==
+// makes a member of nothing, a row of NaNs included (every NaN has one rank, so the ranks alone would say "member").  -0.0 and +0.0
+// share a rank: each is a member of a row that holds the other.  rank_at_c: the rank of boundary c when c < m, ANY value otherwise --
+// the caller must not fetch boundary m (a query above every boundary has c == m), and this function does not look at it then.
+template <typename R>
+__host__ __device__ inline uint32_t search_member(uint32_t c, uint32_t m, R rank_at_c, R v, bool v_is_nan) {
+    return (c < m && rank_at_c == v && !v_is_nan) ? 1u : 0u;
+}
+// whether rank r (sort_rank, ascending) is the NaN class of a B-bit float: its largest rank (an integer's largest rank is its largest value)
+template <typename R, int B, bool FLOAT>
+__host__ __device__ inline bool search_rank_is_nan(R r) {
+    constexpr R sign = static_cast<R>(1) << (B - 1);
+    return FLOAT && r == (sign | (sign - 1));
+}
+
 struct SearchArgs {
     const void *boundaries;   // b_rows rows of m elements of the dtype
     const int64_t *sorter;    // NULL, or b_rows rows of m positions within the row
     const void *queries;      // q_rows rows of q_len elements
-    void *out;                // as many int32 / int64
+    void *out;                // as many int32 / int64; membership form: as many bytes
     uint32_t m, b_rows, q_rows, q_len;
     int right, out64, vec_ok;  // vec_ok: every group of four queries and outputs may move as one aligned vector
+    int member, invert;        // the membership form (right == 0, out64 == 0): out bytes are membership ^ invert
     unsigned long long inf_bits;
     uint32_t chunks_per_row;  // work items per query row
     unsigned long long chunk_len;  // queries of a work item (a multiple of kSearchChunk)

@@ -1,4 +1,5 @@
-"""torch.searchsorted and torch.bucketize drop-ins: where each value of `input` goes in a sorted sequence (vrs_search_sorted).
+"""torch.searchsorted, torch.bucketize and torch.isin drop-ins: where each value of `input` goes in a sorted sequence, and whether it
+is there at all (vrs_search_sorted and its membership form).
 
 One call on torch's current stream.  The library picks a tier from the shape (vrs_search_plan): boundaries that fit a workgroup's LDS
 are searched there, 1- and 2-byte dtypes with many queries through a table of every bit pattern's answer, long sequences with many
@@ -11,7 +12,7 @@ import ctypes
 from . import capi
 from ._torch import aligned, buffers, context_for
 from .capi import VrsError
-from .sort import _dtype_code
+from .sort import _dtype_code, sort_values
 
 TIER_NAMES = {capi.VRS_SEARCH_LDS: "lds", capi.VRS_SEARCH_TABLE: "table", capi.VRS_SEARCH_DIRECT: "direct", capi.VRS_SEARCH_INDEXED: "indexed"}
 
@@ -93,6 +94,59 @@ def searchsorted(sorted_sequence, input, *, out_int32: bool = False, right: bool
     scratch = torch.empty(need.value, dtype=torch.uint8, device=device) if need.value else None
     with buffers(ctx, seq_c, values_c, sorter_c, out, scratch) as (bnd, qry, srt, res, scr):
         ctx.check(lib.vrs_search_sorted(ctx.handle, bnd, nb, m, qry, nq, q_len, code, flags, srt, res, scr))
+    return out
+
+
+def isin(elements, test_elements, *, assume_unique: bool = False, invert: bool = False):
+    """torch.isin(elements, test_elements, assume_unique=, invert=) of tensors on a GPU: a torch.bool tensor of elements' shape, True
+    where the element equals some test element (invert: where it equals none); equal to torch.isin on the CPU bit for bit.
+
+    Two steps on torch's current stream: this library's sort of the flattened test set (values only), then one vrs_search_sorted call
+    in its membership form (VRS_SEARCH_MEMBER, with VRS_SEARCH_MEMBER_INVERT for invert=True) that writes the bool result itself -- no
+    index tensor, no gather, no logical_not.  The tier and the scratch are those vrs_search_plan reports for the shapes.
+    Either argument may be a Python number, not both; a number as `elements` gives a 0-dim result.  Both sides are converted to
+    torch.result_type(elements, test_elements) as torch does, which must be one of the nine dtypes of sort; bool raises torch's own
+    RuntimeError.  -0.0 equals +0.0, and a NaN equals nothing, a NaN among the test elements included.  assume_unique is accepted and
+    changes nothing: duplicates among the test elements never change membership.  An empty `elements` or an empty test set launches
+    nothing.  Refusals (CPU tensors, two devices, 2^32 or more elements on either side, other dtypes) are VrsError and come before any
+    device work."""
+    import torch
+
+    tensors = [t for t in (elements, test_elements) if isinstance(t, torch.Tensor)]
+    if not tensors:
+        _refuse("isin takes a tensor as elements or as test_elements")
+    for t in (elements, test_elements):
+        if not isinstance(t, (torch.Tensor, bool, int, float)):
+            _refuse("elements and test_elements must be tensors or Python numbers")
+    if any(t.dtype == torch.bool if isinstance(t, torch.Tensor) else isinstance(t, bool) for t in (elements, test_elements)):
+        raise RuntimeError("Unsupported input type encountered for isin(): Bool")  # (torch's refusal of a bool on either side, in its words)
+    common = torch.result_type(elements, test_elements)
+    code = _dtype_code(torch, common, "isin")  # (refuses a promoted dtype outside the nine)
+    if not all(t.is_cuda for t in tensors):
+        _refuse("isin takes tensors on a GPU")
+    device = tensors[0].device
+    if tensors[-1].device != device:
+        _refuse("elements and test_elements must be on one device")
+    if any(t.numel() >= 1 << 32 for t in tensors):
+        _refuse("isin takes fewer than 2^32 elements on either side")
+    as_tensor = lambda t: t if isinstance(t, torch.Tensor) else torch.tensor(t, dtype=common, device=device)  # noqa: E731
+    queries = aligned(as_tensor(elements).to(common).contiguous())
+    tests = as_tensor(test_elements).to(common).reshape(-1)
+    nq, m = queries.numel(), tests.numel()
+    if nq == 0:
+        return torch.empty(queries.shape, dtype=torch.bool, device=device)
+    if m == 0:
+        return torch.full(queries.shape, bool(invert), dtype=torch.bool, device=device)
+    bounds = aligned(sort_values(tests))
+    out = torch.empty(queries.shape, dtype=torch.bool, device=device)
+    flags = capi.VRS_SEARCH_MEMBER | (capi.VRS_SEARCH_MEMBER_INVERT if invert else 0)
+    ctx = context_for(device)
+    lib = ctx.lib
+    tier, need = ctypes.c_int(), ctypes.c_uint64()
+    ctx.check(lib.vrs_search_plan(ctx.handle, m, m, nq, nq, code, 0, ctypes.byref(tier), ctypes.byref(need)))
+    scratch = torch.empty(need.value, dtype=torch.uint8, device=device) if need.value else None
+    with buffers(ctx, bounds, queries, out, scratch) as (bnd, qry, res, scr):
+        ctx.check(lib.vrs_search_sorted(ctx.handle, bnd, m, m, qry, nq, nq, code, flags, None, res, scr))
     return out
 
 

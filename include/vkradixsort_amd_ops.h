@@ -108,7 +108,8 @@ int vrs_sort_rank_bytes(int dtype, int *rank_bytes);
  * out_indices[i*k + j] its position relative to the clamped begin; with VRS_TOPK_SORTED slot j holds the j-th entry of the stable
  * order, without it the same m entries in some order.  Slots j in [m, k) of both arrays get 0xFFFFFFFF.  out_indices may be NULL.
  * Bytes of the out buffers past 4 * num_segments * k are never written.  scratch: at least vrs_topk_scratch_bytes(...) bytes (at
- * most 4 n + 16 S k + 1 MiB), contents afterwards unspecified; given that much the call never fails for lack of memory.
+ * most 4 n + 16 S k + 1 MiB) on an 8-byte boundary (its head holds a 64-bit counter; off it: VRS_ERROR_INVALID_ARGUMENT), contents
+ * afterwards unspecified; given that much the call never fails for lack of memory.
  * k == 0 or num_segments == 0: VRS_OK, nothing done.  NULL handles other than out_indices, an unknown key_type or flag bit,
  * num_segments * k >= 2^32 and undersized buffers: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
  * Tiers by clamped length (vrs_topk_tier): up to 8192 keys one workgroup per segment selects inside LDS; longer segments are streamed
@@ -155,10 +156,12 @@ int vrs_topk_stats(vrs_context ctx, uint64_t *lds_segments, uint64_t *block_segm
  *                         torch's rule, a row with any NaN has median NaN
  *   VRS_SELECT_NANMEDIAN  j = (L - nans - 1) / 2 among the non-NaN keys when nans < L (they follow the NaNs when descending), else the
  *                         first NaN
- * scratch: at least vrs_select_scratch_bytes(...) bytes, contents afterwards unspecified; given that much the call never fails for
+ * scratch: at least vrs_select_scratch_bytes(...) bytes on an 8-byte boundary (whatever the dtype: its head holds a 64-bit counter),
+ * contents afterwards unspecified; given that much the call never fails for
  * lack of memory.  num_segments == 0: VRS_OK, nothing done.  An unknown dtype, mode or flag bit, k == 0 with VRS_SELECT_KTH, a NULL
  * context, src, offsets, out_values or scratch, undersized buffers (src: num_elements elements; out_values: num_segments elements;
- * out_indices: num_segments uint32) and 8-byte elements off an 8-byte boundary: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
+ * out_indices: num_segments uint32), 8-byte elements off an 8-byte boundary and a scratch off one: VRS_ERROR_INVALID_ARGUMENT before
+ * anything is enqueued.
  * Digits of at most 11 bits from the top of the dtype's 8 / 16 / 32 / 64 bits (1 / 2 / 3 / 6 levels); a segment is done once the
  * chosen bin holds one key.  Tiers by clamped length (vrs_select_tier, decided by vrs_select_tier_for): ranks that fit 32 KB (8192 keys
  * of up to 4 bytes, 4096 of 8) are read once into the LDS of one workgroup; longer segments are streamed by one workgroup each, one read
@@ -619,9 +622,11 @@ int vrs_compact_stats(vrs_context ctx, uint64_t *count_calls, uint64_t *emit_cal
  * One pass over the keys: tiles of 4096 keys taken in order from a ticket, a head flag per key (i == 0 or k[i] != k[i-1]), ranks by
  * __ballot / mbcnt, the runs in front of a tile by decoupled look-back; the counts from the offsets by a second, short launch.
  * scratch: at least vrs_run_length_encode_scratch_bytes(n, key_bytes, flags) bytes, with VRS_RLE_COUNTS in flags whenever out_counts
- * is given and out_offsets is NULL (the offsets then live in the scratch): at most (VRS_RLE_COUNTS ? 4 n : 0) + n / 256 + 1024 bytes.
- * Contents on entry unspecified, afterwards unspecified.  NULL ctx, keys, out_num_runs or scratch, a key_bytes other than 4 or 8 and
- * undersized buffers (n entries; n + 1 for out_offsets): VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.  Stream-ordered on the
+ * is given and out_offsets is NULL (the offsets then live in the scratch): at most (VRS_RLE_COUNTS ? 4 n : 0) + n / 256 + 1024 bytes,
+ * on an 8-byte boundary (the look-back's status words are 64 bits wide).
+ * Contents on entry unspecified, afterwards unspecified.  NULL ctx, keys, out_num_runs or scratch, a key_bytes other than 4 or 8,
+ * undersized buffers (n entries; n + 1 for out_offsets) and a scratch off an 8-byte boundary: VRS_ERROR_INVALID_ARGUMENT before
+ * anything is enqueued.  Stream-ordered on the
  * context's stream; the call only enqueues (after settling a pending one-call sort).
  */
 enum { VRS_RLE_COUNTS = 1 }; /* scratch flag */
@@ -644,9 +649,10 @@ int vrs_run_length_encode_scratch_bytes(uint32_t num_elements, int key_bytes, in
  * sort sorts them there (vrs_sort_pairs_u32 / vrs_sort_pairs_u64 with the inverse, vrs_sort_keys_u32 / vrs_sort_keys_u64 without), and
  * the run-length encode runs over the sorted ranks, undoing r as it writes out_keys and scattering run ids through the sorted positions.
  * scratch: at least vrs_unique_scratch_bytes(n, key_type, flags) bytes with VRS_UNIQUE_INVERSE / VRS_UNIQUE_COUNTS set for the outputs
- * given: at most (2 * key bytes + (VRS_UNIQUE_INVERSE ? 8 : 0) + (VRS_UNIQUE_COUNTS ? 4 : 0)) * n + n / 256 + 2048 bytes.  Contents on
- * entry unspecified, afterwards unspecified.  NULL ctx, keys, out_keys, out_num_runs or scratch, an unknown key_type and undersized
- * buffers: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
+ * given: at most (2 * key bytes + (VRS_UNIQUE_INVERSE ? 8 : 0) + (VRS_UNIQUE_COUNTS ? 4 : 0)) * n + n / 256 + 2048 bytes, on an
+ * 8-byte boundary (the encode's status words, and 64-bit keys sorted inside it).  Contents on
+ * entry unspecified, afterwards unspecified.  NULL ctx, keys, out_keys, out_num_runs or scratch, an unknown key_type, undersized
+ * buffers and a scratch off an 8-byte boundary: VRS_ERROR_INVALID_ARGUMENT before anything is enqueued.
  * Blocking, as the segmented sorts': after settling a pending one-call sort the call may wait for the inner sort's plan head (bounded by
  * VRS_TUNE_PLAN_WAIT_MS -> VRS_ERROR_TIMEOUT, the encode then not enqueued), never for the sort itself; the inner sort counts in the
  * one-call statistics.

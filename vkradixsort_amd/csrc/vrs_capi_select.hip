@@ -84,6 +84,8 @@ int vrs_select_segments(vrs_context ctx, vrs_buffer src, uint32_t num_elements, 
         return rc;
     if (eb == 8u && ((reinterpret_cast<uintptr_t>(src->ptr) | reinterpret_cast<uintptr_t>(out_values->ptr) | reinterpret_cast<uintptr_t>(scratch->ptr)) & 7u))
         return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "select: 8-byte elements need src, out_values and scratch on 8-byte boundaries");
+    // whatever the dtype: the control block at the scratch's head holds a 64-bit word the classification adds to atomically
+    if (reinterpret_cast<uintptr_t>(scratch->ptr) & 7u) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "select: scratch must be on an 8-byte boundary");
     VRS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = settle_pending(ctx))) return rc;
     if (!ctx->select) ctx->select = new (std::nothrow) vrs_select_state;

@@ -76,6 +76,8 @@ int vrs_topk_segments(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, v
         (rc = check_buffer(ctx, out_keys, slots, "out_keys")) || (out_indices && (rc = check_buffer(ctx, out_indices, slots, "out_indices"))) ||
         (rc = check_buffer(ctx, scratch, L.bytes, "scratch")))
         return rc;
+    // the control block at its head holds a 64-bit word the classification adds to atomically
+    if (reinterpret_cast<uintptr_t>(scratch->ptr) & 7u) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "top-k: scratch must be on an 8-byte boundary");
     VRS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = settle_pending(ctx))) return rc;
     if (!ctx->topk) ctx->topk = new (std::nothrow) vrs_topk_state;

@@ -12,6 +12,10 @@ constexpr int kKnownUniqueFlags = vrs::kUniqueInverse | vrs::kUniqueCounts;
 
 bool known_key_type(int key_type) { return key_type >= vrs::kUniqueU32 && key_type <= vrs::kUniqueF64; }
 
+// the look-back's status words are 64 bits wide and are their own flag: a word that straddles an 8-byte boundary could be seen half
+// written (and 64-bit keys sorted inside unique's scratch sit behind them)
+bool off_status_boundary(vrs_buffer scratch) { return (reinterpret_cast<uintptr_t>(scratch->ptr) & 7u) != 0u; }
+
 // n == 0: R = 0 is the whole result
 int write_no_runs(vrs_context ctx, vrs_buffer out_num_runs) {
     VRS_HIP(ctx, hipMemsetAsync(out_num_runs->ptr, 0, sizeof(uint32_t), ctx->stream));
@@ -45,6 +49,7 @@ int vrs_run_length_encode(vrs_context ctx, vrs_buffer keys, uint32_t num_element
         (out_counts && (rc = check_buffer(ctx, out_counts, wb, "out_counts"))) ||
         (out_run_ids && (rc = check_buffer(ctx, out_run_ids, wb, "out_run_ids"))) || (rc = check_buffer(ctx, scratch, L.bytes, "scratch")))
         return rc;
+    if (off_status_boundary(scratch)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "run-length encode: scratch must be on an 8-byte boundary");
     VRS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = settle_pending(ctx))) return rc;
     if (n == 0u) return write_no_runs(ctx, out_num_runs);
@@ -89,6 +94,7 @@ int vrs_unique(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, int key_
         (out_counts && (rc = check_buffer(ctx, out_counts, wb, "out_counts"))) ||
         (out_inverse && (rc = check_buffer(ctx, out_inverse, wb, "out_inverse"))) || (rc = check_buffer(ctx, scratch, L.bytes, "scratch")))
         return rc;
+    if (off_status_boundary(scratch)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "unique: scratch must be on an 8-byte boundary");
     VRS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = settle_pending(ctx))) return rc;
     if (n == 0u) return write_no_runs(ctx, out_num_runs);

@@ -83,15 +83,35 @@ int vrs_segment_tier_for_u64(uint32_t begin, uint32_t end, uint32_t num_elements
  * NULL ctx or handles, an unknown dtype or flag bit, num_elements not a whole number of rows and undersized buffers:
  * VRS_ERROR_INVALID_ARGUMENT before anything is enqueued; num_elements == 0: VRS_OK, nothing done.  Stream-ordered on the context's
  * stream; both calls only enqueue (after settling a pending one-call sort).
+ *
+ * The mode form (torch.mode): vrs_sort_restore with VRS_SORT_MODE reduces every sorted row to its most frequent value and one place
+ * where it sits in the input.  ranks: what vrs_sort_rank_keys (ascending, out_positions NULL) wrote, followed by a bare-key sort of
+ * every row -- num_elements / row_len = num_rows rows, each sorted ascending; never written.  src: the unsorted input, required, never
+ * written.  A run is a maximal stretch of equal ranks inside one row (runs never continue across a row boundary, even when the next
+ * row begins with the same rank); the modal run of a row is its longest, among equally long ones the one that starts first -- the
+ * smallest value, which is torch's rule.  out_indices_i64[row] = the highest i in [0, row_len) with r(src[row, i]) equal to the modal
+ * rank: the last occurrence.  out_values[row] = src[row, that i], the element's own bits (a zero's sign and a NaN's payload are kept;
+ * under r, -0.0 and +0.0 are one value and every NaN is one value, the largest).  out_values holds num_rows elements of dtype and
+ * out_indices_i64 num_rows int64: both required, nothing beyond num_rows entries is written.
+ * With VRS_SORT_MODE `positions` IS NOT POSITIONS BUT THE CALL'S SCRATCH: at least 8 * num_rows bytes on an 8-byte boundary, required,
+ * its contents unspecified on entry and afterwards -- a caller that hands it the positions of a sort loses them.
+ * The ranks (and the input) are read in tiles of 4096 consecutive elements, whatever the rows; the result does not depend on the tiles,
+ * the grid or the run: the only communication between workgroups is an order-independent atomic maximum (a workgroup may read the
+ * word first and skip a maximum that could not raise it; it never waits for one).
+ * Refused with VRS_ERROR_INVALID_ARGUMENT before anything is enqueued: VRS_SORT_MODE | VRS_SORT_DESCENDING; a NULL src, ranks,
+ * positions, out_values or out_indices_i64; undersized buffers; a scratch off an 8-byte boundary.  vrs_sort_rank_keys takes no
+ * VRS_SORT_MODE (an unknown flag bit there); bit 4 and above are unknown flag bits for both calls.  Both calls look at their flags
+ * before anything else, the context included.  num_elements == 0: VRS_OK, nothing done.  Stream-ordered and enqueue-only (two
+ * memsets and three launches after settling a pending one-call sort); the call never waits for the device.
  */
 typedef enum vrs_sort_dtype {
     VRS_SORT_INT8 = 0, VRS_SORT_UINT8 = 1, VRS_SORT_INT16 = 2, VRS_SORT_INT32 = 3, VRS_SORT_INT64 = 4,
     VRS_SORT_FLOAT16 = 5, VRS_SORT_BFLOAT16 = 6, VRS_SORT_FLOAT32 = 7, VRS_SORT_FLOAT64 = 8
 } vrs_sort_dtype;
-enum { VRS_SORT_DESCENDING = 1 }; /* flags */
+enum { VRS_SORT_DESCENDING = 1, VRS_SORT_MODE = 2 /* vrs_sort_restore only: the mode form */ }; /* flags */
 int vrs_sort_rank_keys(vrs_context ctx, vrs_buffer src, uint32_t num_elements, uint32_t row_len, int dtype, int flags,
                        vrs_buffer out_ranks /* uint32 or uint64 */, vrs_buffer out_positions /* uint32, may be NULL */);
-int vrs_sort_restore(vrs_context ctx, vrs_buffer src, vrs_buffer ranks, vrs_buffer positions /* may be NULL */,
+int vrs_sort_restore(vrs_context ctx, vrs_buffer src, vrs_buffer ranks, vrs_buffer positions /* may be NULL; VRS_SORT_MODE: scratch */,
                      uint32_t num_elements, uint32_t row_len, int dtype, int flags,
                      vrs_buffer out_values /* may be NULL */, vrs_buffer out_indices_i64 /* may be NULL */);
 /* the bytes of one rank of dtype: 4 or 8 (a pure function, needs no device) */

@@ -10,6 +10,8 @@ selection  torch.kthvalue / torch.median / torch.nanmedian drop-ins by a one-ran
 quantile   torch.quantile / torch.nanquantile drop-ins by a multi-rank radix select: up to 16 order statistics per row carried through one
            sequence of reads, values only (quantile_segments over Buffers; quantile, nanquantile for torch tensors)
 sort       torch.sort / torch.argsort drop-ins: any dim, descending, nine dtypes, torch's order bit for bit (sort, sort_values, argsort)
+mode       torch.mode drop-in: the most frequent value of every row and the last index where it sits, by a bare-key sort of the ranks and
+           the mode form of vrs_sort_restore -- the longest run of every sorted row, no position payload through the sort (mode)
 search     torch.searchsorted / torch.bucketize drop-ins over sorted sequences: nine dtypes, N-D, sorter (searchsorted, bucketize);
            torch.isin by a sort of the test set and the search's membership form, a byte per element (isin)
 binning    torch.bincount / torch.histc / torch.histogram drop-ins: counters in LDS or global memory, integer counts converted once
@@ -34,6 +36,7 @@ from .compact import (argwhere, compact_stats, count_nonzero, mask_index, mask_i
                       masked_select, nonzero, where)
 from .engine import (Buffer, ComputePass, Extent3D, GPUContext, MultiRadixSort, MultiRadixSortPass,  # noqa: F401
                      SingleRadixSort, SingleRadixSortPass, generateRandomNumbers)
+from .mode import mode  # noqa: F401
 from .quantile import nanquantile, quantile, quantile_scratch_bytes, quantile_segments, quantile_stats  # noqa: F401
 from .reduce import index_add, index_reduce, reduce_stats, scatter_reduce, segment_reduce  # noqa: F401
 from .repeat import repeat_interleave  # noqa: F401

@@ -107,6 +107,7 @@ RLE_TILE = 4096
 (VRS_SORT_INT8, VRS_SORT_UINT8, VRS_SORT_INT16, VRS_SORT_INT32, VRS_SORT_INT64, VRS_SORT_FLOAT16, VRS_SORT_BFLOAT16, VRS_SORT_FLOAT32,
  VRS_SORT_FLOAT64) = range(9)
 VRS_SORT_DESCENDING = 1
+VRS_SORT_MODE = 2  # vrs_sort_restore only: the mode form (positions is then the call's scratch)
 # sorted-sequence search (vrs_search_sorted): flags, tiers (vrs_search_tier), tuning keys and the library's defaults for them
 VRS_SEARCH_RIGHT, VRS_SEARCH_OUT_INT64 = 1, 2
 VRS_SEARCH_MEMBER, VRS_SEARCH_MEMBER_INVERT = 16, 32  # the membership form (isin): a byte per query; bits 4 and 8 stay refused

@@ -148,7 +148,19 @@ FORM_KNOBS = ["single_max_keys", "one_call_min_keys", "hybrid_min_keys", "pool_m
 # keys the local sort of one top-14-bit bucket can hold (msd_local_capacity): uint32 keys with the 256- / 512-thread workgroup, pairs and 64-bit keys
 LOCAL_SORT_SMALL_KEYS, LOCAL_SORT_MAX_KEYS = 7165, 14333
 LOCAL_SORT_SMALL_PAIRS, LOCAL_SORT_MAX_PAIRS = 6656, 13312  # pairs and 64-bit keys: 512 / 1024-thread workgroups
-HYBRID_MIN_KEYS_DEFAULT = 0  # vrs_capi.hip: os_hybrid_min_keys == 0: the measured crossovers (1.3e7 keys, 2.5e7 pairs, 2e7 64-bit keys)
+HYBRID_MIN_KEYS_DEFAULT = 0  # vrs_tuning.hpp: hybrid_min_keys == 0: the measured crossovers (1.3e7 keys, 2.5e7 pairs, 2e7 64-bit keys)
+# the library's default per tuning key, for the keys that have a *_DEFAULT name above: what GPUContext.tuned(key) returns until the key
+# is set.  tests/test_tuning_cpu.py holds every entry (and every *_MIN / *_MAX) against the table in csrc/vrs_tuning.hpp
+TUNING_DEFAULTS = {
+    VRS_TUNE_ONE_CALL_MIN_KEYS: ONE_CALL_MIN_KEYS_DEFAULT, VRS_TUNE_HYBRID_MIN_KEYS: HYBRID_MIN_KEYS_DEFAULT,
+    VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS: SEGMENT_ONE_CALL_MIN_KEYS_DEFAULT, VRS_TUNE_TOPK_GRID_MIN_KEYS: TOPK_GRID_MIN_KEYS_DEFAULT,
+    VRS_TUNE_SELECT_GRID_MIN_KEYS: SELECT_GRID_MIN_KEYS_DEFAULT, VRS_TUNE_SELECT_COMPACT_DIVISOR: SELECT_COMPACT_DIVISOR_DEFAULT,
+    VRS_TUNE_SEARCH_LDS_BYTES: SEARCH_LDS_BYTES_DEFAULT, VRS_TUNE_SEARCH_TABLE_MIN_QUERIES: SEARCH_TABLE_MIN_QUERIES_DEFAULT,
+    VRS_TUNE_SEARCH_INDEX_MIN_QUERIES: SEARCH_INDEX_MIN_QUERIES_DEFAULT, VRS_TUNE_BINCOUNT_LDS_BYTES: BINCOUNT_LDS_BYTES_DEFAULT,
+    VRS_TUNE_REDUCE_CHUNK_ROWS: REDUCE_CHUNK_ROWS_DEFAULT, VRS_TUNE_REDUCE_LANE_ROWS: REDUCE_LANE_ROWS_DEFAULT,
+    VRS_TUNE_SCAN_TILE_ROWS: SCAN_TILE_ROWS_DEFAULT, VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS: SCAN_SINGLE_PASS_MIN_ROWS_DEFAULT,
+    VRS_TUNE_SCAN_SPIN_BUDGET: SCAN_SPIN_BUDGET_DEFAULT, VRS_TUNE_COMPACT_TILE_ELEMS: COMPACT_TILE_ELEMS_DEFAULT,
+}
 
 
 class PushConstants(Structure):

@@ -62,7 +62,7 @@ class _Counted:
         self.flags = aligned(flags.contiguous()).reshape(-1)
         self.n, self.code = n, _flag_code(torch, flags.dtype, name)
         self.ctx = context_for(flags.device)
-        tile = self.ctx.tuning.get(capi.VRS_TUNE_COMPACT_TILE_ELEMS, capi.COMPACT_TILE_ELEMS_DEFAULT)
+        tile = self.ctx.tuned(capi.VRS_TUNE_COMPACT_TILE_ELEMS)
         need = capi.query_u64("vrs_compact_scratch_bytes", n, tile)
         self.scratch = torch.empty(need, dtype=torch.uint8, device=flags.device)
         got = ctypes.c_uint64()

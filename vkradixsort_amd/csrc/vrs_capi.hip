@@ -55,7 +55,7 @@ int ensure_scratch(vrs_context ctx, uint32_t W) {
     }
     // the fused single-launch prefix needs all G chunk workgroups resident at once
     ctx->scratch.fused_max_chunks =
-        ctx->fused_prefix ? std::min<uint32_t>(ctx->scratch_chunks, static_cast<uint32_t>(ctx->scatter.compute_units)) : 0u;
+        ctx->tune.fused_prefix ? std::min<uint32_t>(ctx->scratch_chunks, static_cast<uint32_t>(ctx->scatter.compute_units)) : 0u;
     if (++ctx->scratch.epoch == 0) ctx->scratch.epoch = 1;
     return VRS_OK;
 }
@@ -126,7 +126,7 @@ int atomic_rank_selftest(vrs_context ctx, uint32_t rounds, uint32_t seed, uint64
 // on XCC b % 8" (any fixed function of b % 8 will do, a single XCC included).  That placement is observed, not
 // promised, so it is probed here; the kernels re-check it per workgroup and stay correct without it.
 int probe_xcc_map(vrs_context ctx, int stray_block) {
-    constexpr uint32_t kBlocks = 4096;
+    constexpr uint32_t kBlocks = vrs::kXccProbeBlocks;
     uint32_t *d = nullptr;
     VRS_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d), kBlocks * sizeof(uint32_t)));
     std::vector<uint32_t> h(kBlocks, 0);
@@ -195,7 +195,7 @@ int create_context(int device_ordinal, hipStream_t borrowed, bool borrow, vrs_co
         ctx->owns_stream = false;
         // whoever lends a stream waits on it with calls of his own (hipStreamSynchronize, torch.cuda.synchronize): what a sort puts
         // on such a stream must be the whole sort when the call returns -- the blocking form is the default there
-        ctx->os_async = false;
+        ctx->tune.async = false;
     } else {
         e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
@@ -586,186 +586,46 @@ int vrs_set_tuning(vrs_context ctx, int key, int value) {
         const int rc = settle_pending(ctx);
         if (rc) return rc;
     }
-    switch (key) {
-        case VRS_TUNE_XCD_REMAP:
-            ctx->xcd_remap = value != 0;
-            return VRS_OK;
+    if (const char *refusal = vrs::tuning_refusal(key, value)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, refusal);
+    vrs::tuning_store(ctx->tune, key, value);
+    switch (key) {  // what a key does beside (or instead of) its row's store
         case VRS_TUNE_SCATTER_VARIANT:
             ctx->scatter.variant = value;
-            return VRS_OK;
-        case VRS_TUNE_FUSED_PREFIX:
-            ctx->fused_prefix = value != 0;
-            return VRS_OK;
-        case VRS_TUNE_RANK_MODE: {
-            if (value == 1) {
-                ctx->scatter.atomic_rank = false;
-            } else if (value == 2) {
-                ctx->scatter.atomic_rank = true;
-            } else if (value == 0) {
-                ctx->scatter.atomic_rank = ctx->atomic_rank_verified;
-            } else {
-                return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "rank mode must be 0 (auto), 1 (ballot) or 2 (atomic)");
-            }
-            return VRS_OK;
-        }
-        case VRS_TUNE_ONE_CALL_MIN_KEYS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "one-call threshold must be >= 0");
-            ctx->one_call_min_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_DEBUG_MISPLACE_STREAMS:
-            ctx->os_misplace = value != 0;
-            return VRS_OK;
+            break;
+        case VRS_TUNE_RANK_MODE:  // 0 auto, 1 ballot, 2 atomic
+            ctx->scatter.atomic_rank = value == 2 || (value == 0 && ctx->atomic_rank_verified);
+            break;
         case VRS_TUNE_HYBRID:
-            ctx->os_hybrid = value != 0;
             ctx->os_wide_refused = false;  // 64-bit keys: forget an earlier refusal
             ctx->os_wide_skipped = 0;
-            return VRS_OK;
-        case VRS_TUNE_HYBRID_MIN_KEYS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "hybrid threshold must be >= 0");
-            ctx->os_hybrid_min_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
+            break;
         case VRS_TUNE_HYBRID_FAST_COUNT:
-            if (value < 0 || value > 2) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "fast count mode must be 0, 1 or 2");
-            ctx->os_fast_count = value;
             ctx->os_fast_count_armed[0] = ctx->os_fast_count_armed[1] = false;
-            return VRS_OK;
-        case VRS_TUNE_FUSED_PLAN:
-            ctx->os_fused_plan = value != 0;
-            return VRS_OK;
-        case VRS_TUNE_SINGLE_MAX_KEYS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "single-launch threshold must be >= 0");
-            ctx->single_max_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_LOOKBACK_SPIN_BUDGET:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "spin budget must be >= 0");
-            ctx->os_spin_budget = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_DEBUG_HOLD_TILE:
-            ctx->os_hold_tile = value;
-            return VRS_OK;
-        case VRS_TUNE_ASYNC_SORT:
-            ctx->os_async = value != 0;
-            return VRS_OK;
-        case VRS_TUNE_PLAN_WAIT_MS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the plan wait limit must be >= 0 ms");
-            ctx->os_plan_wait_ms = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_MSD_RESERVE:
-            if (value < 0 || value > 2) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "MSD reservation must be 0 (never) or 1 / 2 (bare keys of the hybrid form)");
-            ctx->os_reserve = value;
-            return VRS_OK;
+            break;
         case VRS_TUNE_MSD_POOL:
-            if (value < 0 || value > 2) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pool form must be 0 (never), 1 (adaptive) or 2 (always tried)");
-            ctx->os_pool = value;
             ctx->os_pool_skip = 0;
-            return VRS_OK;
+            break;
         case VRS_TUNE_DEBUG_XCC_STRAY_BLOCK:
-            if (value >= 4096) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the probe has 4096 blocks (a negative value probes again without a stray one)");
             return probe_xcc_map(ctx, value);  // (a negative value probes again as at creation; a pending sort was settled above)
         case VRS_TUNE_DEBUG_XCC_ROTATE: {
-            if (value < 0 || value > 7) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "rotate the probed placement by 0 .. 7 places");
             if (const int rc = probe_xcc_map(ctx)) return rc;
             const unsigned sh = 8u * static_cast<unsigned>(value);
             if (sh) ctx->xcc_map = (ctx->xcc_map >> sh) | (ctx->xcc_map << (64u - sh));
-            return VRS_OK;
+            break;
         }
         case VRS_TUNE_MSD_POOL_TOP_BITS:
-            if (value < 6 || value > 8) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pool form's first pass sorts by 6, 7 (the default) or 8 bits");
-            ctx->os_pool_top_bits = value;
+        case VRS_TUNE_MSD_POOL_SUB_BITS:
             ctx->os_pool_layout_valid = false;
-            return VRS_OK;
-        case VRS_TUNE_MSD_POOL_PAIRS:
-            ctx->os_pool_pairs = value != 0 ? 1 : 0;
-            return VRS_OK;
+            break;
         case VRS_TUNE_DEBUG_POOL_NO_MEMORY:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "allocations left to fail: 0 or more");
             ctx->os_pool_fail_alloc = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_MSD_POOL_REUSE_LAYOUT:
-            ctx->os_pool_reuse = value != 0;
-            ctx->os_pool_reuse_rooms = value == 1;
+            break;
+        case VRS_TUNE_MSD_POOL_REUSE_LAYOUT:  // (the row stores pool_reuse)
+            ctx->tune.pool_reuse_rooms = value == 1;
             ctx->os_pool_layout_valid = false;
             ctx->os_pool_stale_run = ctx->os_pool_reuse_pause = 0;
-            return VRS_OK;
-        case VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the segmented sorts' one-call threshold must be >= 0");
-            ctx->seg_one_call_min_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_TOPK_GRID_MIN_KEYS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the top-k grid tier's threshold must be >= 0");
-            ctx->topk_grid_min_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SELECT_GRID_MIN_KEYS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the selection's grid tier threshold must be >= 0");
-            ctx->select_grid_min_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SELECT_COMPACT_DIVISOR:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the selection's compaction divisor must be >= 0");
-            ctx->select_compact_divisor = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SEARCH_LDS_BYTES:
-            if (value < 0 || value > 160 * 1024) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the search's LDS capacity must be 0 .. 163840 bytes");
-            ctx->search_lds_bytes = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SEARCH_TABLE_MIN_QUERIES:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the search's table threshold must be >= 0");
-            ctx->search_table_min_queries = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SEARCH_INDEX_MIN_QUERIES:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the search's index threshold must be >= 0");
-            ctx->search_index_min_queries = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_BINCOUNT_LDS_BYTES:
-            if (value < 0 || value > 160 * 1024) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the counting kernels' LDS capacity must be 0 .. 163840 bytes");
-            ctx->bincount_lds_bytes = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_REDUCE_CHUNK_ROWS:
-            if (value < 64 || value > 4096) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the reduction's chunk must be 64 .. 4096 rows");
-            ctx->reduce_chunk_rows = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_REDUCE_LANE_ROWS:
-            if (value < 0 || value > 64) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the reduction's lane map takes 0 .. 64 rows");
-            ctx->reduce_lane_rows = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SCAN_TILE_ROWS:
-            if (value < 256 || value > 8192 || value % 256 != 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's tile must be a multiple of 256 in 256 .. 8192 rows");
-            ctx->scan_tile_rows = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS:
-            if (value < 0) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's single pass starts at 0 (never) or more rows");
-            ctx->scan_single_pass_min_rows = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_SCAN_SPIN_BUDGET:
-            if (value < 0 || value > (1 << 20)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the scan's spin budget must be 0 .. 1048576 polls");
-            ctx->scan_spin_budget = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_COMPACT_TILE_ELEMS:
-            if (value < 4096 || value > 65536 || value % 4096 != 0)
-                return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the compaction's tile must be a multiple of 4096 in 4096 .. 65536 elements");
-            ctx->compact_tile_elems = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_MSD_POOL_PAIRS_PACKED:
-            if (value < -1 || value > 1) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pairs' packed local sort: -1 (by size), 0 (never) or 1 (always)");
-            ctx->os_pool_pairs_packed = value;
-            return VRS_OK;
-        case VRS_TUNE_MSD_POOL_SUB_BITS:
-            if (value != 0 && (value < 6 || value > 8)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pool form's second pass sorts by 6, 7 or 8 bits (0 = by size)");
-            ctx->os_pool_sub_bits = value;
-            ctx->os_pool_layout_valid = false;
-            return VRS_OK;
-        case VRS_TUNE_MSD_POOL_MIN_KEYS:
-            if (value < (1 << 22)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "the pool form takes 2^22 keys or more");
-            ctx->os_pool_min_keys = static_cast<uint32_t>(value);
-            return VRS_OK;
-        case VRS_TUNE_DIGIT_TABLE_GROUPS:
-            if (value != 0 && value != 8 && value != 16 && value != 32)
-                return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "digit table groups must be 0 (by size), 8, 16 or 32");
-            if (static_cast<uint32_t>(value) % vrs::kStreams != 0)
-                return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "digit table groups must be a multiple of the stream count");
-            ctx->os_groups = static_cast<uint32_t>(value);
-            return VRS_OK;
-        default:
-            return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "unknown tuning key");
+            break;
     }
+    return VRS_OK;
 }
 }  // extern "C"

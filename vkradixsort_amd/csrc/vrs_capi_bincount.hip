@@ -64,7 +64,7 @@ int vrs_bin_count_plan(vrs_context ctx, uint32_t num_bins, int weight_dtype, int
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
     if (!tier || !scratch_bytes) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "an output pointer is NULL");
     if (const int rc = check_counters(ctx, num_bins, weight_dtype, out_dtype)) return rc;
-    *tier = vrs::bin_count_tier(num_bins, vrs::bin_counter_bytes(weight_dtype), ctx->bincount_lds_bytes);
+    *tier = vrs::bin_count_tier(num_bins, vrs::bin_counter_bytes(weight_dtype), ctx->tune.bincount_lds_bytes);
     *scratch_bytes = vrs::bin_count_layout(num_bins, weight_dtype, out_dtype).bytes;
     return VRS_OK;
 }
@@ -141,7 +141,7 @@ int vrs_bin_count(vrs_context ctx, vrs_buffer values, uint32_t num_values, int d
         a.lo = lo;
         a.hi = hi;
         a.compute_units = ctx->scatter.compute_units;
-        const int tier = vrs::bin_count_tier(num_bins, static_cast<uint32_t>(cb), ctx->bincount_lds_bytes);
+        const int tier = vrs::bin_count_tier(num_bins, static_cast<uint32_t>(cb), ctx->tune.bincount_lds_bytes);
         VRS_HIP(ctx, vrs::launch_bin_count(ctx->stream, a, dtype, mode, weight_dtype, tier));
         ctx->bincount_calls[tier] += 1u;
     }

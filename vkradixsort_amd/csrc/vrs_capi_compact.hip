@@ -35,8 +35,8 @@ bool off_boundary(const void *p, size_t bytes) { return (reinterpret_cast<uintpt
 int check_common(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, vrs_buffer scratch, vrs::CompactLayout *layout) {
     if (!vrs::compact_dtype_known(dtype)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "compact: dtype is one of vrs_sort_dtype or VRS_COMPACT_BOOL");
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
-    if (const int rc = check_span(ctx, n, ctx->compact_tile_elems)) return rc;
-    *layout = vrs::compact_layout(n, ctx->compact_tile_elems);
+    if (const int rc = check_span(ctx, n, ctx->tune.compact_tile_elems)) return rc;
+    *layout = vrs::compact_layout(n, ctx->tune.compact_tile_elems);
     if (n == 0u) return VRS_OK;
     int rc;
     const size_t flag_bytes = static_cast<size_t>(n) * static_cast<size_t>(vrs::compact_dtype_bytes(dtype));
@@ -174,7 +174,7 @@ int vrs_compact_count(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, 
     vrs::CompactCountArgs a{};
     a.flags = flags->ptr;
     a.n = n;
-    a.T = ctx->compact_tile_elems;
+    a.T = ctx->tune.compact_tile_elems;
     a.dtype = dtype;
     a.scratch = static_cast<char *>(scratch->ptr);
     a.out_count = out_count_device ? static_cast<long long *>(out_count_device->ptr) : nullptr;
@@ -245,7 +245,7 @@ int vrs_compact_emit(vrs_context ctx, vrs_buffer flags, uint64_t n, int dtype, v
     vrs::CompactEmitArgs a{};
     a.flags = flags->ptr;
     a.n = n;
-    a.T = ctx->compact_tile_elems;
+    a.T = ctx->tune.compact_tile_elems;
     a.dtype = dtype;
     a.scratch = static_cast<const char *>(scratch->ptr);
     a.limit = R;

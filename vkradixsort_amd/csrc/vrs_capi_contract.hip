@@ -75,7 +75,7 @@ int run_sort_stage(vrs_context ctx, vrs_buffer keys_in, vrs_buffer keys_out, vrs
     VRS_HIP(ctx, vrs::launch_scatter(ctx->stream, keys_in->ptr, keys_out->ptr,
                                      pairs ? static_cast<const uint32_t *>(values_in->ptr) : nullptr,
                                      pairs ? static_cast<uint32_t *>(values_out->ptr) : nullptr, ctx->scratch.offsets,
-                                     n, pc->g_shift, launch_W, launch_B, ctx->xcd_remap, ctx->scatter, ev, nullptr,
+                                     n, pc->g_shift, launch_W, launch_B, ctx->tune.xcd_remap, ctx->scatter, ev, nullptr,
                                      row_stride, key_bytes));
     return VRS_OK;
 }
@@ -249,7 +249,7 @@ int vrs_range_partition(vrs_context ctx, vrs_buffer keys_in, vrs_buffer keys_out
     if ((rc = profile_events(ctx, VRS_KERNEL_SCATTER, &ev))) return rc;
     VRS_HIP(ctx, vrs::launch_range_partition(ctx->stream, static_cast<const uint32_t *>(keys_in->ptr),
                                              static_cast<uint32_t *>(keys_out->ptr), ctx->scratch.offsets, n, W,
-                                             ctx->xcd_remap, ctx->scatter.atomic_rank,
+                                             ctx->tune.xcd_remap, ctx->scatter.atomic_rank,
                                              static_cast<const uint32_t *>(splitters->ptr), num_splitters, ev));
     return VRS_OK;
 }

@@ -94,7 +94,7 @@ int vrs_msd_partition_signal_u32(vrs_context ctx, vrs_buffer keys, vrs_buffer ou
     a.forced = vrs::kForcedIfCounted;
     a.key_bytes = 4;
     a.setup = setup;
-    // (the context's test hooks os_hold_tile / os_misplace do not apply to a partition: hold_tile, misplace and key_base keep their defaults)
+    // (the context's test hooks tune.hold_tile / tune.misplace do not apply to a partition: hold_tile, misplace and key_base keep their defaults)
     a.reserve = reserves(ctx, n, false) ? ctx->os_msd_plan : nullptr;
     VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, a, ev));
     return VRS_OK;
@@ -271,7 +271,7 @@ int vrs_msd_finish_grouped_split_u32(vrs_context ctx, vrs_buffer grouped, vrs_bu
     // the buckets' slack regions, the local sort finishes.  Where it cannot run -- the form switched off, no shape for these buckets,
     // fewer keys than its fixed costs are worth -- the counted finish takes over.
     const vrs::PoolShape shape = vrs::pool_grouped_shape(n, top_bytes);
-    if (ctx->os_pool == 0 || !reserves(ctx, n, false) || shape.sub_bits == 0u || n < (1u << 20) || n >= (1u << 30) || !ctx->xcc_map_valid ||
+    if (ctx->tune.pool == 0 || !reserves(ctx, n, false) || shape.sub_bits == 0u || n < (1u << 20) || n >= (1u << 30) || !ctx->xcc_map_valid ||
         !ctx->atomic_rank_verified || !ctx->scatter.atomic_rank)
         return counted();
     VRS_HIP(ctx, hipSetDevice(ctx->device));

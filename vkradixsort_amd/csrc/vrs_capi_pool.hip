@@ -80,7 +80,7 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     const uint32_t n = st.n;
     int rc;
     const bool pairs = st.vptr[0] != nullptr;
-    const vrs::PoolCut cut = vrs::pool_cut(n, pairs, ctx->os_pool_top_bits, pairs ? 0 : ctx->os_pool_sub_bits);
+    const vrs::PoolCut cut = vrs::pool_cut(n, pairs, ctx->tune.pool_top_bits, pairs ? 0 : ctx->tune.pool_sub_bits);
     const vrs::PoolShape shape{cut.sub_bits, cut.local};
     const uint32_t top_bits = cut.top_bits, top_bytes = 1u << top_bits;
     st.pool_top_bits = top_bits;
@@ -102,10 +102,10 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
         pv.slack_values = ctx->os_pool_slack_vals;
         pv.status = ctx->os_status;
         pv.status_words = status_words(ctx);
-        pv.spin_budget = ctx->os_spin_budget;
-        pv.hold_tile = ctx->os_hold_tile;
+        pv.spin_budget = ctx->tune.spin_budget;
+        pv.hold_tile = ctx->tune.hold_tile;
         pv.top_bits = top_bits;
-        pv.packed = ctx->os_pool_pairs_packed;
+        pv.packed = ctx->tune.pool_pairs_packed;
     }
     const uint32_t c = st.cur;
     uint32_t *home = static_cast<uint32_t *>(st.kptr[c]), *partner = static_cast<uint32_t *>(st.kptr[c ^ 1u]);
@@ -129,7 +129,7 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     form.setup = launch_setup(ctx);
     form.top_bits = top_bits;
     form.pv = pairs ? &pv : nullptr;
-    st.pool_reused = ctx->os_pool_reuse && ctx->os_pool_layout_valid && ctx->os_pool_layout_n == n && ctx->os_pool_layout_base == st.key_base &&
+    st.pool_reused = ctx->tune.pool_reuse && ctx->os_pool_layout_valid && ctx->os_pool_layout_n == n && ctx->os_pool_layout_base == st.key_base &&
                      (ctx->os_pool_layout_sub_bits >> 8) == top_bits;
     // Back-off: a workload whose distribution changes from sort to sort at equal n (sorted, then random; alternating key ranges) finds
     // every kept layout stale -- two passes, a host round trip and the whole sort again, each time.  After two stale layouts in a row the
@@ -158,7 +158,7 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     pa.keys_out = partner;
     pa.overflow = ctx->os_pool_overflow;
     pa.overflow_capacity = room;
-    pa.misplace = ctx->os_misplace;
+    pa.misplace = ctx->tune.misplace;
     VRS_HIP(ctx, vrs::launch_pool_pass_a(ctx->stream, pa, ev));
     vrs::PoolPlanArgs pl{};
     pl.form = form;
@@ -167,7 +167,7 @@ int one_read_enqueue_pool(vrs_context ctx, const OneReadGeometry &g) {
     pl.regions = partner;
     pl.overflow = ctx->os_pool_overflow;
     pl.sub_bits = shape.sub_bits;
-    pl.keep_rooms = st.pool_reused && ctx->os_pool_reuse_rooms && (ctx->os_pool_layout_sub_bits & 255u) == shape.sub_bits;
+    pl.keep_rooms = st.pool_reused && ctx->tune.pool_reuse_rooms && (ctx->os_pool_layout_sub_bits & 255u) == shape.sub_bits;
     VRS_HIP(ctx, vrs::launch_pool_plan(ctx->stream, pl));
     if ((rc = profile_events(ctx, VRS_KERNEL_POOL_PASS_B, &ev))) return rc;
     vrs::PoolPassBArgs pb{};
@@ -220,7 +220,7 @@ int vrs_pool_form_shape(uint32_t n, uint32_t *sub_bits, uint32_t *bucket_capacit
 
 int vrs_pool_form_shape_ex(uint32_t n, int pairs, int top_bits_setting, uint32_t *first_pass_bits, uint32_t *second_pass_bits, uint32_t *bucket_capacity,
                            uint64_t *scratch_bytes) {
-    if (top_bits_setting == 0) top_bits_setting = 7;  // the library's default cut (vrs_context_t::os_pool_top_bits)
+    if (top_bits_setting == 0) top_bits_setting = vrs::kPoolTopBitsDefault;  // the library's default cut
     if (top_bits_setting < 6 || top_bits_setting > 8) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "top_bits: 0 (the default), 6, 7 or 8");
     const bool takes = n >= (1u << 22) && (pairs ? n <= vrs::pool_max_pairs() : n <= vrs::kPoolMaxKeys);
     const vrs::PoolCut cut = takes ? vrs::pool_cut(n, pairs != 0, top_bits_setting, 0) : vrs::PoolCut{0u, 0u, 0u};

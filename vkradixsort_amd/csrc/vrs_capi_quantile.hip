@@ -169,8 +169,8 @@ int vrs_quantile_segments(vrs_context ctx, vrs_buffer src, uint32_t num_elements
     a.n = num_elements;
     a.num_segments = num_segments;
     a.num_q = num_q;
-    a.grid_min_keys = ctx->select_grid_min_keys;
-    a.compact_divisor = ctx->select_compact_divisor;
+    a.grid_min_keys = ctx->tune.select_grid_min_keys;
+    a.compact_divisor = ctx->tune.select_compact_divisor;
     a.dtype = dtype;
     a.interpolation = interpolation;
     a.flags = flags;

@@ -136,11 +136,11 @@ int vrs_scan_rows(vrs_context ctx, vrs_buffer values, uint32_t num_segments, uin
     int rc;
     if ((rc = check_kind(ctx, dtype, out_dtype, op))) return rc;
     if (!ctx) return fail(nullptr, VRS_ERROR_INVALID_ARGUMENT, "context is NULL");
-    if ((rc = check_shape(ctx, num_segments, num_rows, row_width, ctx->scan_tile_rows))) return rc;
+    if ((rc = check_shape(ctx, num_segments, num_rows, row_width, ctx->tune.scan_tile_rows))) return rc;
     if (num_segments == 0u || num_rows == 0u) return VRS_OK;
     const bool pairs = op >= vrs::kScanMax;
-    const int tier = vrs::scan_tier(num_segments, num_rows, row_width, out_dtype, op, ctx->scan_tile_rows, ctx->scan_single_pass_min_rows);
-    const vrs::ScanLayout l = vrs::scan_layout(num_segments, num_rows, row_width, out_dtype, op, ctx->scan_tile_rows, tier);
+    const int tier = vrs::scan_tier(num_segments, num_rows, row_width, out_dtype, op, ctx->tune.scan_tile_rows, ctx->tune.scan_single_pass_min_rows);
+    const vrs::ScanLayout l = vrs::scan_layout(num_segments, num_rows, row_width, out_dtype, op, ctx->tune.scan_tile_rows, tier);
     if (!values || !out || (pairs && !out_indices) || (l.bytes != 0u && !scratch))
         return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL (values, out, out_indices for max and min, scratch)");
     const size_t count = static_cast<size_t>(num_segments) * num_rows * row_width;
@@ -168,12 +168,12 @@ int vrs_scan_rows(vrs_context ctx, vrs_buffer values, uint32_t num_segments, uin
     a.S = num_segments;
     a.L = num_rows;
     a.C = row_width;
-    a.T = ctx->scan_tile_rows;
+    a.T = ctx->tune.scan_tile_rows;
     a.dtype = dtype;
     a.out_dtype = out_dtype;
     a.op = op;
     a.tier = tier;
-    a.spin_budget = ctx->scan_spin_budget;
+    a.spin_budget = ctx->tune.scan_spin_budget;
     a.takeovers = ctx->scan_takeovers;
     VRS_HIP(ctx, vrs::launch_scan_rows(ctx->stream, a, l, ctx->scatter.compute_units));
     ++ctx->scan_calls[tier];

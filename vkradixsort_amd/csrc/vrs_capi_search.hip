@@ -98,8 +98,8 @@ int vrs_search_plan(vrs_context ctx, uint32_t num_boundaries, uint32_t boundary_
     if (!tier || !scratch_bytes) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "an output pointer is NULL");
     Shape s;
     if (const int rc = check_shape(ctx, num_boundaries, boundary_row_len, num_queries, query_row_len, dtype, &s)) return rc;
-    *tier = vrs::search_tier(s.m, s.b_rows, s.q_per_row, dtype, ctx->search_lds_bytes, ctx->search_table_min_queries,
-                             ctx->search_index_min_queries);
+    *tier = vrs::search_tier(s.m, s.b_rows, s.q_per_row, dtype, ctx->tune.search_lds_bytes, ctx->tune.search_table_min_queries,
+                             ctx->tune.search_index_min_queries);
     *scratch_bytes = vrs::search_layout(s.m, s.b_rows, dtype, has_sorter != 0, *tier).bytes;
     return VRS_OK;
 }
@@ -133,8 +133,8 @@ int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_bound
     if (!out || (num_boundaries != 0u && !boundaries)) return fail(ctx, VRS_ERROR_INVALID_ARGUMENT, "a buffer handle is NULL");
     const int invert = (flags & vrs::kSearchMemberInvert) ? 1 : 0;
     const size_t eb = static_cast<size_t>(vrs::sort_dtype_bytes(dtype)), ob = member ? 1u : (flags & vrs::kSearchOutInt64) ? 8u : 4u;
-    const int tier = vrs::search_tier(s.m, s.b_rows, s.q_per_row, dtype, ctx->search_lds_bytes, ctx->search_table_min_queries,
-                                      ctx->search_index_min_queries);
+    const int tier = vrs::search_tier(s.m, s.b_rows, s.q_per_row, dtype, ctx->tune.search_lds_bytes, ctx->tune.search_table_min_queries,
+                                      ctx->tune.search_index_min_queries);
     const vrs::SearchLayout L = vrs::search_layout(s.m, s.b_rows, dtype, sorter != nullptr, tier);
     if ((rc = check_buffer(ctx, queries, num_queries * eb, "queries")) || (rc = check_buffer(ctx, out, num_queries * ob, "out")) ||
         (num_boundaries != 0u && (rc = check_buffer(ctx, boundaries, num_boundaries * eb, "boundaries"))) ||
@@ -175,7 +175,7 @@ int vrs_search_sorted(vrs_context ctx, vrs_buffer boundaries, uint32_t num_bound
     const uint64_t per_chunk = (static_cast<uint64_t>(s.q_len) + chunks - 1u) / chunks;
     a.chunk_len = (per_chunk + vrs::kSearchChunk - 1u) / vrs::kSearchChunk * vrs::kSearchChunk;
     a.chunks_per_row = static_cast<uint32_t>((static_cast<uint64_t>(s.q_len) + a.chunk_len - 1u) / a.chunk_len);
-    VRS_HIP(ctx, vrs::launch_search(ctx->stream, a, dtype, tier, ctx->search_lds_bytes, L, scratch ? static_cast<char *>(scratch->ptr) : nullptr));
+    VRS_HIP(ctx, vrs::launch_search(ctx->stream, a, dtype, tier, ctx->tune.search_lds_bytes, L, scratch ? static_cast<char *>(scratch->ptr) : nullptr));
     ctx->search_calls[tier] += 1u;
     return VRS_OK;
 }

@@ -51,7 +51,7 @@ int segmented(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buffer 
 
     const bool wide = key_bytes == 8;
     const uint32_t block_cap = vrs::seg_block_cap(wide, pairs);
-    const uint32_t min_keys = ctx->seg_one_call_min_keys;
+    const uint32_t min_keys = ctx->tune.seg_one_call_min_keys;
     vrs::SegLists lists{};
     lists.cap[vrs::kSegListWaveSmall] = list_cap(n, num_segments, 2u);
     lists.cap[vrs::kSegListWave] = list_cap(n, num_segments, vrs::kSegWaveSmallCap + 1u);

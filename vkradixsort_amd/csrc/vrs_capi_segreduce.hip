@@ -153,7 +153,7 @@ int vrs_segment_reduce(vrs_context ctx, vrs_buffer values, uint32_t num_rows, ui
     const size_t eb = static_cast<size_t>(vrs::sort_dtype_bytes(dtype));
     const size_t value_bytes = static_cast<size_t>(num_rows) * row_width * eb, out_bytes = static_cast<size_t>(num_segments) * row_width * eb;
     const size_t order_bytes = order ? static_cast<size_t>(num_rows) * sizeof(uint32_t) : 0u, offset_bytes = (static_cast<size_t>(num_segments) + 1u) * sizeof(uint32_t);
-    const vrs::ReduceLayout L = vrs::reduce_layout(num_rows, row_width, num_segments, dtype, ctx->reduce_chunk_rows);
+    const vrs::ReduceLayout L = vrs::reduce_layout(num_rows, row_width, num_segments, dtype, ctx->tune.reduce_chunk_rows);
     if ((num_rows != 0u && (rc = check_buffer(ctx, values, value_bytes, "values"))) ||
         (order && num_rows != 0u && (rc = check_buffer(ctx, order, order_bytes, "order"))) ||
         (rc = check_buffer(ctx, offsets, offset_bytes, "offsets")) || (init && (rc = check_buffer(ctx, init, out_bytes, "init"))) ||
@@ -182,8 +182,8 @@ int vrs_segment_reduce(vrs_context ctx, vrs_buffer values, uint32_t num_rows, ui
     a.n = num_rows;
     a.C = row_width;
     a.num_segments = num_segments;
-    a.chunk_rows = ctx->reduce_chunk_rows;
-    a.lane_rows = ctx->reduce_lane_rows;
+    a.chunk_rows = ctx->tune.reduce_chunk_rows;
+    a.lane_rows = ctx->tune.reduce_lane_rows;
     a.dtype = dtype;
     a.op = op;
     a.stats = s->stats;

@@ -36,7 +36,7 @@ int wait_for_host_word(vrs_context ctx, const std::function<bool()> &arrived, bo
             }
             if (q != hipErrorNotReady) return fail_hip(ctx, "hipStreamQuery (waiting for the sort plan)", q);
             const auto waited = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-            if (ctx->os_plan_wait_ms != 0 && waited > static_cast<long long>(ctx->os_plan_wait_ms))
+            if (ctx->tune.plan_wait_ms != 0 && waited > static_cast<long long>(ctx->tune.plan_wait_ms))
                 return fail(ctx, VRS_ERROR_TIMEOUT,
                             "the one-call sort's plan did not arrive in time: the stream is held up by earlier work "
                             "(VRS_TUNE_PLAN_WAIT_MS; the sort itself is still queued -- vrs_sort_settle may be called again)");
@@ -83,7 +83,7 @@ OneReadGeometry one_read_geometry(vrs_context ctx, const vrs_context_t::OneRead 
     // flushes 3 * G * 256 counters -- a fixed cost that only large inputs amortise (10^7 keys: 20 vs 34 us for the
     // counting read, 3 * 10^7: 47 vs 61, 10^8: a tie; profiles/labs/r02_groups_and_fused_plan.txt); the hybrid form's
     // bucket histogram needs the 8-group tables to fit beside it in LDS
-    g.G = st.msd_capable ? 8u : ctx->os_groups ? ctx->os_groups : (n < (1u << 26) ? 8u : 32u);
+    g.G = st.msd_capable ? 8u : ctx->tune.groups ? ctx->tune.groups : (n < (1u << 26) ? 8u : 32u);
     g.T = vrs::onesweep_tile_keys(st.key_bytes);
     g.tiles_total = (n + g.T - 1) / g.T;
     const uint32_t group_tiles = (g.tiles_total + g.G - 1) / g.G;  // tiles per pass-0 group (slice of the input)
@@ -215,8 +215,8 @@ int one_read_lookback_pass(vrs_context ctx, vrs_context_t::OneRead &st, uint32_t
     a.forced = forced;
     a.key_bytes = st.key_bytes;
     a.setup = launch_setup(ctx);
-    a.hold_tile = ctx->os_hold_tile;
-    a.misplace = ctx->os_misplace;
+    a.hold_tile = ctx->tune.hold_tile;
+    a.misplace = ctx->tune.misplace;
     VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, a, ev));
     return VRS_OK;
 }
@@ -225,10 +225,10 @@ int one_read_lookback_pass(vrs_context ctx, vrs_context_t::OneRead &st, uint32_t
 // entry point that is about to enqueue a reserving pass calls this first.
 bool reserves(vrs_context ctx, uint32_t n, bool pairs) {
     (void)n;  // (measured from 1.5e7 to 1e8 keys: 2 to 5 % of the sort at every size the hybrid form takes)
-    return !pairs && ctx->os_reserve != 0;
+    return !pairs && ctx->tune.reserve != 0;
 }
 int reservation_begin(vrs_context ctx) {
-    if (!ctx->os_reserve || !ctx->os_msd_plan) return VRS_OK;
+    if (!ctx->tune.reserve || !ctx->os_msd_plan) return VRS_OK;
     if (ctx->os_cursors_open)
         VRS_HIP(ctx, hipMemsetAsync(reinterpret_cast<char *>(ctx->os_msd_plan) + offsetof(vrs::MsdPlan, cursor_a), 0, vrs::kMsdCursorBytes, ctx->stream));
     ctx->os_cursors_open = true;
@@ -299,15 +299,15 @@ int one_read_hybrid_tail(vrs_context ctx, vrs_context_t::OneRead &st, const OneR
 // what the dispatcher's decision function looks at, read off the context
 vrs::SortKnobs sort_knobs(vrs_context ctx) {
     vrs::SortKnobs k;
-    k.single_max_keys = ctx->single_max_keys;
-    k.one_call_min_keys = ctx->one_call_min_keys;
-    k.hybrid_min_keys = ctx->os_hybrid_min_keys;
-    k.pool_min_keys = ctx->os_pool_min_keys;
-    k.hybrid = ctx->os_hybrid ? 1 : 0;
-    k.pool = ctx->os_pool;
-    k.pool_pairs = ctx->os_pool_pairs;
-    k.reserve = ctx->os_reserve;
-    k.groups = ctx->os_groups;
+    k.single_max_keys = ctx->tune.single_max_keys;
+    k.one_call_min_keys = ctx->tune.one_call_min_keys;
+    k.hybrid_min_keys = ctx->tune.hybrid_min_keys;
+    k.pool_min_keys = ctx->tune.pool_min_keys;
+    k.hybrid = ctx->tune.hybrid ? 1 : 0;
+    k.pool = ctx->tune.pool;
+    k.pool_pairs = ctx->tune.pool_pairs;
+    k.reserve = ctx->tune.reserve;
+    k.groups = ctx->tune.groups;
     k.xcc_map_valid = ctx->xcc_map_valid;
     k.atomic_rank = ctx->atomic_rank_verified && ctx->scatter.atomic_rank;
     k.pool_skip = ctx->os_pool_skip;
@@ -337,14 +337,14 @@ int one_read_enqueue(vrs_context ctx) {
         // sort of this kind took the form (or always: VRS_TUNE_HYBRID_FAST_COUNT = 2) -- a refusal of a blind tail costs a second
         // counting read, and data that was refused once is usually refused again
         st.blind_tail = st.msd_capable && st.deferred &&
-                        (wide || ctx->os_fast_count == 2 || (ctx->os_fast_count == 1 && ctx->os_fast_count_armed[pairs ? 1 : 0]));
+                        (wide || ctx->tune.fast_count == 2 || (ctx->tune.fast_count == 1 && ctx->os_fast_count_armed[pairs ? 1 : 0]));
         // Fast count: the counting read of a hybrid-capable sort fills only the bucket histogram (1 LDS add per key instead
         // of 5).  If the plan then refuses the hybrid form, nothing has been moved and the sort starts over as an LSD sort
         // -- a second counting read.  Adaptive (default): fast only while the context's last hybrid-capable sort took the
         // hybrid form; after a refusal the next ones count everything again (a refusal then costs nothing extra) until one
         // is taken.  A sort enqueued completely (async mode) always counts fast: a refusal must find every key in place.
-        st.fast_count = st.msd_capable && (wide || st.blind_tail || ctx->os_fast_count == 2 ||
-                                           (ctx->os_fast_count == 1 && ctx->os_fast_count_armed[pairs ? 1 : 0]));
+        st.fast_count = st.msd_capable && (wide || st.blind_tail || ctx->tune.fast_count == 2 ||
+                                           (ctx->tune.fast_count == 1 && ctx->os_fast_count_armed[pairs ? 1 : 0]));
     }
     const bool msd = st.msd_capable && st.group == 0;
     const OneReadGeometry g = one_read_geometry(ctx, st);
@@ -357,7 +357,7 @@ int one_read_enqueue(vrs_context ctx) {
         // sorts of this size do not ask again at once: the adaptive skip, as after a refusal)
         st.no_pool = true;
         st.pool = false;
-        if (ctx->os_pool == 1) {
+        if (ctx->tune.pool == 1) {
             ctx->os_pool_skip = 15;
             ctx->os_pool_skip_n = n;
         }
@@ -426,12 +426,12 @@ int one_read_enqueue(vrs_context ctx) {
         c.status_words = zero_words;
         c.setup = setup;
         c.geo = plan_geometry(ctx, g, n, st.stamp);
-        if (ctx->os_fused_plan) {
+        if (ctx->tune.fused_plan) {
             c.fused_plan = ctx->os_plan;
             c.fused_done = ctx->os_ticket;
         }
         VRS_HIP(ctx, vrs::launch_digit_tables(ctx->stream, c, ev));
-        if (!ctx->os_fused_plan) {
+        if (!ctx->tune.fused_plan) {
             vrs::PlanArgs p{};
             p.tables = ctx->os_tables;
             p.plan = ctx->os_plan;
@@ -466,8 +466,8 @@ int one_read_enqueue(vrs_context ctx) {
         a.forced = vrs::kForcedNo;
         a.key_bytes = key_bytes;
         a.setup = setup;
-        a.hold_tile = ctx->os_hold_tile;
-        a.misplace = ctx->os_misplace;
+        a.hold_tile = ctx->tune.hold_tile;
+        a.misplace = ctx->tune.misplace;
         a.key_base = st.key_base;
         a.reserve = reserves(ctx, n, pairs) ? ctx->os_msd_plan : nullptr;
         VRS_HIP(ctx, vrs::launch_onesweep_scatter(ctx->stream, a, ev));
@@ -535,7 +535,7 @@ int one_read_complete(vrs_context ctx, bool *done) {
                     pv.status = ctx->os_status;
                     pv.status_words = status_words(ctx);
                     pv.top_bits = st.pool_top_bits;
-                    pv.packed = ctx->os_pool_pairs_packed;
+                    pv.packed = ctx->tune.pool_pairs_packed;
                 }
                 st.pool_retried = true;
                 st.pool_local = local;
@@ -577,7 +577,7 @@ int one_read_complete(vrs_context ctx, bool *done) {
             return one_read_enqueue(ctx);
         }
         ctx->os_pool_refusals++;
-        if (ctx->os_pool == 1) {
+        if (ctx->tune.pool == 1) {
             ctx->os_pool_skip = 15;
             ctx->os_pool_skip_n = n;
         }
@@ -694,7 +694,7 @@ int sort_one_read(vrs_context ctx, vrs_buffer keys, vrs_buffer keys_tmp, vrs_buf
     st.vptr[1] = values ? values_tmp->ptr : nullptr;
     st.n = n;
     st.key_bytes = key_bytes;
-    st.deferred = ctx->os_async;
+    st.deferred = ctx->tune.async;
     int rc = reprobe_if_drifted(ctx);
     if (rc == VRS_OK) rc = one_read_enqueue(ctx);
     if (rc) {

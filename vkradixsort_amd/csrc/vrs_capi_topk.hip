@@ -90,7 +90,7 @@ int vrs_topk_segments(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, v
     a.n = num_elements;
     a.num_segments = num_segments;
     a.k = k;
-    a.grid_min_keys = ctx->topk_grid_min_keys;
+    a.grid_min_keys = ctx->tune.topk_grid_min_keys;
     a.key_type = key_type;
     a.flags = flags;
     a.out_keys = static_cast<uint32_t *>(out_keys->ptr);
@@ -109,11 +109,11 @@ int vrs_topk_segments(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, v
     vrs_buffer_t kv = stack_view(ctx, area, vb), kt = stack_view(ctx, area + sk, vb);
     vrs_buffer_t vv = stack_view(ctx, area + 2u * static_cast<size_t>(sk), vb), vt = stack_view(ctx, area + 3u * static_cast<size_t>(sk), vb);
     vrs_buffer_t ov = stack_view(ctx, a.out_keys, (static_cast<size_t>(num_segments) + 1u) * sizeof(uint32_t));
-    const uint32_t saved = ctx->seg_one_call_min_keys;
-    ctx->seg_one_call_min_keys = 0u;
+    const uint32_t saved = ctx->tune.seg_one_call_min_keys;
+    ctx->tune.seg_one_call_min_keys = 0u;
     rc = out_indices ? vrs_sort_segments_pairs_u32(ctx, &kv, &kt, &vv, &vt, sk, &ov, num_segments)
                      : vrs_sort_segments_u32(ctx, &kv, &kt, sk, &ov, num_segments);
-    ctx->seg_one_call_min_keys = saved;
+    ctx->tune.seg_one_call_min_keys = saved;
     if (rc) return rc;
     VRS_HIP(ctx, vrs::launch_topk_sort_back(ctx->stream, a, L));
     return VRS_OK;

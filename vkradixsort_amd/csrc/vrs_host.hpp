@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "vrs_kernels.h"
+#include "vrs_tuning.hpp"
 
 struct vrs_segmented_state;  // vrs_capi_segmented.hip
 struct vrs_topk_state;       // vrs_capi_topk.hip
@@ -54,8 +55,7 @@ struct vrs_context_t {
         int key_bytes = 4;
         bool valid = false;
     } sub_cache;
-    bool xcd_remap = true;
-    bool fused_prefix = true;
+    vrs::Tuning tune;  // what vrs_set_tuning stores (vrs_tuning.hpp): every setting a caller can make, but scatter.variant / .atomic_rank
     vrs::ScatterLaunch scatter;
     bool atomic_rank_verified = false;  // device self-test result (context creation)
     vrs_buffer sort_hist = nullptr;     // histogram table owned by the one-call entry points
@@ -67,8 +67,6 @@ struct vrs_context_t {
     std::vector<EventPair> events[VRS_KERNEL_COUNT];
     size_t events_used[VRS_KERNEL_COUNT] = {};
     // one-call sort for large N (K5 in vrs_one_call.hip)
-    uint32_t one_call_min_keys = 1u << 13;  // measured: the one-read form wins from the single-launch threshold on (profiles/r02_one_call_crossover.csv)
-    uint32_t single_max_keys = 4096;     // one-call uint32 key sorts up to this size run as ONE single_radixsort launch
     uint32_t *os_tables = nullptr;       // [4][kStreams][256] digit tables, zero between sorts
     vrs::OnesweepPlan *os_plan = nullptr;
     uint32_t *os_status = nullptr;       // look-back status rows
@@ -78,11 +76,6 @@ struct vrs_context_t {
     vrs::OnesweepPlanHead *os_host_head_dev = nullptr;  // the same memory as the device sees it
     uint32_t os_stamp = 0;               // stamp of the most recent plan (never 0)
     uint32_t *os_ticket = nullptr;       // fused plan: ticket word of the counting read's workgroups (zero between launches)
-    bool os_fused_plan = false;          // the counting read's last workgroup makes the plan (VRS_TUNE_FUSED_PLAN)
-    uint32_t os_groups = 0;              // groups per pass of the counting read: 8, 16, 32 or 0 = by size, VRS_TUNE_DIGIT_TABLE_GROUPS
-    uint32_t os_spin_budget = 4096;      // polls of an unpublished look-back row before a tile recounts, VRS_TUNE_LOOKBACK_SPIN_BUDGET
-    int os_hold_tile = -1;               // test hook, VRS_TUNE_DEBUG_HOLD_TILE
-    bool os_misplace = false;            // test hook, VRS_TUNE_DEBUG_MISPLACE_STREAMS
     uint32_t drift_seen = 0;             // OnesweepPlanHead::drift (host copy) as of the last probe
     uint64_t reprobes = 0;               // probes run because sorts reported workgroups off the probed placement
     bool xcc_map_valid = false;          // the probe found block b on an XCC that depends on b % 8 only
@@ -90,29 +83,18 @@ struct vrs_context_t {
     uint64_t os_lookback_passes = 0;
     uint64_t os_relaunched_passes = 0;
     // hybrid form (K5b)
-    bool os_hybrid = true;               // VRS_TUNE_HYBRID
-    int os_fast_count = 1;               // VRS_TUNE_HYBRID_FAST_COUNT: 0 never, 1 adaptive, 2 always
     bool os_fast_count_armed[2] = {false, false};  // adaptive: the context's last hybrid-capable sort of keys [0] / pairs [1] took the hybrid form
     bool os_wide_refused = false;        // 64-bit keys: the last attempt at the hybrid form was refused
     uint32_t os_wide_skipped = 0;        //   ... sorts since (every 16th tries again)
     uint64_t os_hybrid_recounts = 0;     // sorts that started over as LSD sorts after a fast count and a refusal
-    // VRS_TUNE_HYBRID_MIN_KEYS; 0 (default) = the measured crossovers per kind of sort: 1.3e7 bare uint32 keys (small buckets are
-    // sorted one wave per bucket: profiles/labs/r03_hybrid_by_size.txt), 2.5e7 pairs, 2e7 64-bit keys (profiles/labs/r02_*).  A set
-    // value v means v keys, 5/8 v pairs, v/2 64-bit keys.
-    uint32_t os_hybrid_min_keys = 0u;
     uint32_t *os_msd_counts = nullptr;   // [16384] top-14-bit histogram + [8][256] top-byte counts per pass-0 group, zero between sorts
     vrs::MsdPlan *os_msd_plan = nullptr;
     vrs::OnesweepPlan *os_plan_a = nullptr;  // seeds and streams of the first MSD pass
     uint64_t os_hybrid_sorts = 0;        // one-call sorts that took the hybrid form
     uint64_t os_fallback_passes = 0;
     uint64_t os_skipped_passes = 0;      // identity passes (one digit value holds every key) the one-call sort left out     // passes the one-call sort ran through the contract path (unbalanced streams)
-    bool os_async = true;                // VRS_TUNE_ASYNC_SORT (default 1): the one-call sorts return without waiting for the plan; vrs_sort_settle finishes them
-    uint32_t os_plan_wait_ms = 60000;    // VRS_TUNE_PLAN_WAIT_MS: longest wait for a plan's head (0 = no limit)
-    int os_reserve = 1;                  // VRS_TUNE_MSD_RESERVE: the MSD passes over bare keys reserve their output instead of looking back
-                                         // (1 or 2: whenever the hybrid form runs on bare keys; 0: never)
     // pool form (vrs_msd_pool.hip): the hybrid form of bare uint32 keys without the counting read
-    int os_pool = 1;                     // VRS_TUNE_MSD_POOL: 0 never, 1 (default) adaptive -- after a refusal the next 15 such sorts take the counted form --, 2 always tried
-    uint32_t os_pool_skip = 0;           // adaptive: hybrid-capable sorts of bare keys left before the pool form is tried again
+    uint32_t os_pool_skip = 0;           // adaptive (tune.pool == 1): hybrid-capable sorts of bare keys left before the pool form is tried again
     uint32_t os_pool_skip_n = 0;         //   keys of the sort whose refusal started the count: a sort of another size class (beyond a factor of two) is another workload and starts afresh
     vrs::PoolPlan *os_pool_plan = nullptr;
     uint32_t *os_pool_overflow = nullptr;  // overflow regions of the first pass
@@ -121,22 +103,10 @@ struct vrs_context_t {
     uint32_t os_pool_slack_cap = 0;        //   slots
     uint32_t *os_pool_overflow_vals = nullptr, *os_pool_slack_vals = nullptr;  // key + payload pairs: the payloads' twins of the two (made with the first pool sort of pairs)
     uint32_t os_pool_vals_overflow_cap = 0, os_pool_vals_slack_cap = 0;
-    int os_pool_top_bits = 7;              // VRS_TUNE_MSD_POOL_TOP_BITS: how a sort's 16384 buckets are cut between the two passes -- 7 + 7 bits (default: the first pass, which
-                                           // reads cold input, writes 64-key segments instead of 32-key ones: pairs -2.4 %, 10^7 keys -2.5 %, 10^8 keys -1 %), 8 + 6, or 6 + 8
-    int os_pool_pairs = 1;                 // VRS_TUNE_MSD_POOL_PAIRS: key + payload pairs may take the (stable) pool form
-    int os_pool_pairs_packed = -1;         // VRS_TUNE_MSD_POOL_PAIRS_PACKED: the pairs' local sort in its packed form: -1 by size, 0 never, 1 always
     uint64_t os_pool_pair_sorts = 0;
     uint64_t os_pool_sorts = 0, os_pool_refusals = 0, os_pool_retries = 0;  // (retries: sorts whose local sort was enqueued again in a larger shape)
-    uint32_t os_pool_min_keys = 1u << 22;   // VRS_TUNE_MSD_POOL_MIN_KEYS: the form's own floor -- with one wave per small bucket it beats the LSD passes from there on (labs/r05_pool_form.txt section 6)
-    int os_pool_sub_bits = 0;               // VRS_TUNE_MSD_POOL_SUB_BITS: 0 = by size (pool_shape), 6 or 7
     uint32_t os_pool_epoch = 0;             // pool sorts / finishes enqueued: its parity picks the PoolPlan::fail word of each
-    // The regions of the first pass, kept from one sort to the next (VRS_TUNE_MSD_POOL_REUSE_LAYOUT, default on): a sort of the same
-    // size and key floor as the context's last TAKEN pool sort runs its first pass in the regions that sort's sample laid out -- no
-    // sample and layout kernel (13 us and two launch gaps at 10^8 keys).  Nothing is trusted: a region that does not fit, a key
-    // outside the kept range flag the sort as ever; a refusal forgets the layout and the re-run samples.
-    bool os_pool_reuse = true;
-    bool os_pool_reuse_rooms = true;      // ... and the buckets' slack regions with them (the plan kernel then samples nothing): VRS_TUNE_MSD_POOL_REUSE_LAYOUT = 2 keeps the first pass's regions only
-    bool os_pool_layout_valid = false;
+    bool os_pool_layout_valid = false;      // the regions of the first pass, kept from one sort to the next (tune.pool_reuse)
     uint32_t os_pool_layout_n = 0, os_pool_layout_base = 0, os_pool_layout_sub_bits = 0;
     uint32_t os_pool_stale_run = 0, os_pool_reuse_pause = 0;  // kept layouts found stale in a row / sorts left that sample for themselves although a layout is kept
     uint32_t os_pool_fail_alloc = 0;       // VRS_TUNE_DEBUG_POOL_NO_MEMORY: allocations of the pool form's scratch left to fail (test hook)
@@ -172,36 +142,22 @@ struct vrs_context_t {
     uint32_t os_msd_half_stamp = 0;      // stamp of the most recent vrs_msd_finish_u32's plan
     // segmented sorts (vrs_capi_segmented.hip)
     vrs_segmented_state *seg = nullptr;
-    uint32_t seg_one_call_min_keys = 1u << 20;  // VRS_TUNE_SEGMENT_ONE_CALL_MIN_KEYS
     // top-k selection (vrs_capi_topk.hip)
     vrs_topk_state *topk = nullptr;
-    uint32_t topk_grid_min_keys = 1u << 17;  // VRS_TUNE_TOPK_GRID_MIN_KEYS (vrs::kTopkDefaultGridMinKeys)
-    // one-rank selection (vrs_capi_select.hip); the defaults are vrs_select.hpp's kSelDefault*
+    // one-rank selection (vrs_capi_select.hip)
     vrs_select_state *select = nullptr;
-    uint32_t select_grid_min_keys = 1u << 17;  // VRS_TUNE_SELECT_GRID_MIN_KEYS
-    uint32_t select_compact_divisor = 16u;     // VRS_TUNE_SELECT_COMPACT_DIVISOR
-    // multi-rank selection (vrs_capi_quantile.hip): reads the two settings above; its own device counters
+    // multi-rank selection (vrs_capi_quantile.hip): its own device counters
     unsigned long long *quantile_stats = nullptr;  // [4] cumulative segments per tier and grid slots that sieved
-    // sorted-sequence search (vrs_capi_search.hip); the defaults are vrs_search.hpp's kSearchDefault*
-    uint32_t search_lds_bytes = 64u * 1024u;      // VRS_TUNE_SEARCH_LDS_BYTES
-    uint32_t search_table_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_TABLE_MIN_QUERIES
-    uint32_t search_index_min_queries = 1u << 16;  // VRS_TUNE_SEARCH_INDEX_MIN_QUERIES
+    // sorted-sequence search (vrs_capi_search.hip)
     uint64_t search_calls[4] = {};                // calls per tier (vrs_search_stats)
-    // counting (vrs_capi_bincount.hip); the default is vrs_bincount.hpp's kBinCountDefaultLdsBytes
-    uint32_t bincount_lds_bytes = 64u * 1024u;    // VRS_TUNE_BINCOUNT_LDS_BYTES
+    // counting (vrs_capi_bincount.hip)
     uint64_t bincount_calls[2] = {};              // calls per tier (vrs_bin_count_stats)
-    // segmented reduction (vrs_capi_segreduce.hip); the defaults are vrs_reduce_order.hpp's kReduce*Default
+    // segmented reduction (vrs_capi_segreduce.hip)
     vrs_reduce_state *reduce = nullptr;
-    uint32_t reduce_chunk_rows = 512u;            // VRS_TUNE_REDUCE_CHUNK_ROWS
-    uint32_t reduce_lane_rows = 16u;              // VRS_TUNE_REDUCE_LANE_ROWS
-    // prefix scan (vrs_capi_scan.hip); the defaults are vrs_scan_order.hpp's kScan*Default
-    uint32_t scan_tile_rows = 2048u;              // VRS_TUNE_SCAN_TILE_ROWS
-    uint32_t scan_single_pass_min_rows = 1u << 20;  // VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS
-    uint32_t scan_spin_budget = 4096u;            // VRS_TUNE_SCAN_SPIN_BUDGET
+    // prefix scan (vrs_capi_scan.hip)
     uint64_t scan_calls[3] = {};                  // calls per tier (vrs_scan_stats)
     unsigned long long *scan_takeovers = nullptr; // device counter: words a waiting wave of the single pass computed itself
-    // ordered compaction (vrs_capi_compact.hip); the default is vrs_compact_order.hpp's kCompactTileDefault
-    uint32_t compact_tile_elems = 16384u;         // VRS_TUNE_COMPACT_TILE_ELEMS
+    // ordered compaction (vrs_capi_compact.hip)
     uint64_t compact_calls[2] = {};               // count calls, emit calls (vrs_compact_stats)
     uint64_t compact_elements = 0;                // elements the count calls were given
 };
@@ -283,13 +239,13 @@ inline void rearm_counting_tables(vrs_context ctx) {
     if (ctx->os_tables) (void)hipMemsetAsync(ctx->os_tables, 0, kDigitTableBytes, ctx->stream);
     if (ctx->os_msd_counts) (void)hipMemsetAsync(ctx->os_msd_counts, 0, kMsdCountBytes, ctx->stream);
 }
-// what every launch of this context is given (the test hooks os_hold_tile / os_misplace are NOT part of it: each call site says
+// what every launch of this context is given (the test hooks tune.hold_tile / tune.misplace are NOT part of it: each call site says
 // whether they apply)
 inline vrs::LaunchSetup launch_setup(vrs_context ctx) {
     vrs::LaunchSetup s{};
     s.atomic_rank = ctx->scatter.atomic_rank;
     s.xcc_map = ctx->xcc_map;
-    s.spin_budget = ctx->os_spin_budget;
+    s.spin_budget = ctx->tune.spin_budget;
     s.drift = drift_word(ctx);
     s.compute_units = ctx->scatter.compute_units;
     return s;

@@ -11,6 +11,7 @@
 // form down with `no_pool` / `no_hybrid` set: the same function answers for the retry.
 #pragma once
 #include "vrs_kernels.h"
+#include "vrs_tuning.hpp"
 
 namespace vrs {
 
@@ -18,15 +19,15 @@ enum SortFormId : int { kFormNone = 0, kFormSingle = 1, kFormContract = 2, kForm
 
 struct SortKnobs {
     // settings (vrs_set_tuning) and what the context found out about the device
-    uint32_t single_max_keys = 4096;      // VRS_TUNE_SINGLE_MAX_KEYS
-    uint32_t one_call_min_keys = 1u << 13;  // VRS_TUNE_ONE_CALL_MIN_KEYS (0 = never: always the contract stages)
-    uint32_t hybrid_min_keys = 0;         // VRS_TUNE_HYBRID_MIN_KEYS (0 = the measured crossovers: 1.3e7 keys, 2.5e7 pairs, 2e7 64-bit keys)
-    uint32_t pool_min_keys = 1u << 22;    // VRS_TUNE_MSD_POOL_MIN_KEYS
-    int hybrid = 1;                       // VRS_TUNE_HYBRID
-    int pool = 1;                         // VRS_TUNE_MSD_POOL: 0 never, 1 adaptive, 2 always
-    int pool_pairs = 1;                   // VRS_TUNE_MSD_POOL_PAIRS
-    int reserve = 1;                      // VRS_TUNE_MSD_RESERVE
-    uint32_t groups = 0;                  // VRS_TUNE_DIGIT_TABLE_GROUPS (0 = by size)
+    uint32_t single_max_keys = kSingleDefaultMaxKeys;     // VRS_TUNE_SINGLE_MAX_KEYS
+    uint32_t one_call_min_keys = kOneCallDefaultMinKeys;  // VRS_TUNE_ONE_CALL_MIN_KEYS (0 = never: always the contract stages)
+    uint32_t hybrid_min_keys = kHybridDefaultMinKeys;     // VRS_TUNE_HYBRID_MIN_KEYS (0 = the measured crossovers: 1.3e7 keys, 2.5e7 pairs, 2e7 64-bit keys)
+    uint32_t pool_min_keys = kPoolDefaultMinKeys;         // VRS_TUNE_MSD_POOL_MIN_KEYS
+    int hybrid = kHybridDefault ? 1 : 0;                  // VRS_TUNE_HYBRID
+    int pool = kPoolDefault;                              // VRS_TUNE_MSD_POOL: 0 never, 1 adaptive, 2 always
+    int pool_pairs = kPoolPairsDefault;                   // VRS_TUNE_MSD_POOL_PAIRS
+    int reserve = kReserveDefault;                        // VRS_TUNE_MSD_RESERVE
+    uint32_t groups = kGroupsDefault;                     // VRS_TUNE_DIGIT_TABLE_GROUPS (0 = by size)
     bool xcc_map_valid = true;            // the placement probe found "block b on the XCC of b % 8"
     bool atomic_rank = true;              // the lane-order self-test passed and the atomic ranking is in effect
     // what the context remembers of earlier sorts

@@ -116,7 +116,11 @@ class GPUContext:
 
     def setTuning(self, key: int, value: int) -> None:
         self.check(self._lib.vrs_set_tuning(self.handle, key, value))
-        self.tuning[key] = value  # (what was set and accepted: the wrappers size scratch buffers from it)
+        self.tuning[key] = value  # (only what was set and accepted; tuned() adds the defaults)
+
+    def tuned(self, key: int) -> int:
+        """The value in effect for `key`: what setTuning stored, else the library's default (the wrappers size scratch buffers from it)."""
+        return self.tuning.get(key, capi.TUNING_DEFAULTS[key])
 
     def __enter__(self):
         self.init()

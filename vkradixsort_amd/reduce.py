@@ -64,7 +64,7 @@ def _reduce_rows(values, order, offsets, num_segments: int, op: int, init):
     code = _dtype_code(torch, values.dtype)
     ctx = context_for(device)
     lib = ctx.lib
-    chunk_rows = ctx.tuning.get(capi.VRS_TUNE_REDUCE_CHUNK_ROWS, capi.REDUCE_CHUNK_ROWS_DEFAULT)
+    chunk_rows = ctx.tuned(capi.VRS_TUNE_REDUCE_CHUNK_ROWS)
     need = capi.query_u64("vrs_segment_reduce_scratch_bytes", n, C, num_segments, code, chunk_rows)
     scratch = torch.empty(need, dtype=torch.uint8, device=device)
     with buffers(ctx, values, order, offsets, init, out, scratch) as (val, ordr, offs, ini, res, scr):

@@ -77,8 +77,7 @@ def _scan_rows(src, dim: int, op: int, out_dtype):
     src = aligned(src.contiguous())
     code, out_code = _dtype_code(torch, src.dtype, "scan"), _dtype_code(torch, out_dtype, "scan")
     ctx = context_for(device)
-    tile_rows = ctx.tuning.get(capi.VRS_TUNE_SCAN_TILE_ROWS, capi.SCAN_TILE_ROWS_DEFAULT)
-    min_rows = ctx.tuning.get(capi.VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS, capi.SCAN_SINGLE_PASS_MIN_ROWS_DEFAULT)
+    tile_rows, min_rows = ctx.tuned(capi.VRS_TUNE_SCAN_TILE_ROWS), ctx.tuned(capi.VRS_TUNE_SCAN_SINGLE_PASS_MIN_ROWS)
     need = capi.query_u64("vrs_scan_scratch_bytes", S, L, C, code, out_code, op, tile_rows, min_rows)
     scratch = torch.empty(need, dtype=torch.uint8, device=device)
     with buffers(ctx, src, out, idx, scratch) as (val, res, ind, scr):

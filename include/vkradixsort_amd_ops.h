@@ -648,7 +648,16 @@ int vrs_compact_stats(vrs_context ctx, uint64_t *count_calls, uint64_t *emit_cal
  * undersized buffers (n entries; n + 1 for out_offsets) and a scratch off an 8-byte boundary: VRS_ERROR_INVALID_ARGUMENT before
  * anything is enqueued.  Stream-ordered on the
  * context's stream; the call only enqueues (after settling a pending one-call sort).
+ * THE ROW FORM: key_bytes = 4 or 8 | VRS_UNIQUE_COLUMNS(C) with C >= 2 (C of 0 or 1 is the form above, bit for bit) encodes maximal
+ * runs of bit-identical consecutive rows (torch.unique_consecutive(x, dim=0)): num_elements counts rows, `keys` holds n x C words
+ * row-major, out_keys has room for n x C words of which R x C are written (the R rows, by a short launch of its own), and out_offsets,
+ * out_counts and out_run_ids count rows.  A lane compares a row's first 8 bytes with those in front as the word form compares keys and
+ * reads the columns behind them only when these are equal.  scratch: always with room for the offsets (they serve the rows and the
+ * counts when out_offsets is NULL), whatever `flags` says: at most 4 n + n / 256 + 2048 bytes.  n x C >= 2^32, a negative key_bytes
+ * and an unknown low byte are refused like the other arguments.
  */
+/* the columns per row of the row forms of vrs_run_length_encode (in key_bytes) and vrs_unique (in key_type): bits 8 and up */
+#define VRS_UNIQUE_COLUMNS(c) ((int)(c) << 8)
 enum { VRS_RLE_COUNTS = 1 }; /* scratch flag */
 int vrs_run_length_encode(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, int key_bytes, vrs_buffer out_keys,
                           vrs_buffer out_offsets, vrs_buffer out_counts, vrs_buffer out_run_ids, vrs_buffer out_num_runs,
@@ -676,6 +685,18 @@ int vrs_run_length_encode_scratch_bytes(uint32_t num_elements, int key_bytes, in
  * Blocking, as the segmented sorts': after settling a pending one-call sort the call may wait for the inner sort's plan head (bounded by
  * VRS_TUNE_PLAN_WAIT_MS -> VRS_ERROR_TIMEOUT, the encode then not enqueued), never for the sort itself; the inner sort counts in the
  * one-call statistics.
+ * THE ROW FORM: key_type = a vrs_unique_key_type | VRS_UNIQUE_COLUMNS(C) with C >= 2 (C of 0 or 1 is the form above, bit for bit) gives
+ * the distinct rows of an n x C matrix (torch.unique(x, dim=0)): num_elements counts rows, `keys` holds n x C words row-major, rows are
+ * ordered lexicographically by r of every word and are equal when bit-identical; out_keys has room for n x C words of which R x C are
+ * written (the input's own bits), out_counts and out_inverse count rows.  Pipeline: the columns are grouped from the last backwards into
+ * groups of at most 8 bytes of ranks (two 4-byte columns, the more significant in the high half, or one 8-byte column; a lone 4-byte
+ * column left over is column 0 with a 32-bit key), ceil(C * word / 8) rounds; per round, least significant group first, one kernel
+ * packs the group's ranks of the rows in their current order (round 1 reads them where they lie, later rounds gather through the
+ * positions) and the stable vrs_sort_pairs_u64 / _u32 sorts (key, position); the encode then compares the top group's sorted keys and
+ * fetches the remaining columns through the positions only for a pair whose top groups are equal; a last short launch gathers the R
+ * rows.  The call may wait for every inner sort's plan head.  scratch: the same for every C, key type and flags: at most
+ * 28 n + n / 256 + 4096 bytes (two key buffers of 8 bytes per row, the positions and their partner, the run offsets).
+ * n x C >= 2^32, a negative key_type and an unknown low byte are refused like the other arguments.
  */
 typedef enum vrs_unique_key_type {
     VRS_UNIQUE_U32 = 0, VRS_UNIQUE_I32 = 1, VRS_UNIQUE_F32 = 2,

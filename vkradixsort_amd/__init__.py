@@ -28,7 +28,8 @@ repeat     torch.repeat_interleave drop-in: run-length decode, the undo of uniqu
            identity form of the sorted search (a merge: boundaries read once, indices written once), then index_select
            (repeat_interleave)
 unique     run-length encoding and unique by sort + encode (run_length_encode / unique_keys over Buffers, unique / unique_consecutive
-           for torch tensors)
+           for torch tensors); with dim=d (columns=C over Buffers) the distinct rows: LSD rounds of pack + stable pair sort over groups
+           of columns, then the encode with a row head rule
 """
 from .binning import bincount, bincount_stats, histc, histogram  # noqa: F401
 from .capi import PushConstants, VrsError, load_library  # noqa: F401

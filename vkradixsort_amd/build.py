@@ -21,7 +21,7 @@ HIP_SOURCES = [CSRC / name for name in ("vrs_contract.hip", "vrs_one_call.hip", 
                                         "vrs_capi.hip", "vrs_capi_contract.hip", "vrs_capi_sort.hip", "vrs_capi_pool.hip", "vrs_capi_msd.hip", "vrs_dist.hip",
                                         "vrs_segmented.hip", "vrs_capi_segmented.hip", "vrs_topk.hip", "vrs_capi_topk.hip", "vrs_select.hip", "vrs_capi_select.hip",
                                         "vrs_quantile.hip", "vrs_capi_quantile.hip",
-                                        "vrs_unique.hip", "vrs_capi_unique.hip", "vrs_sort_rank.hip", "vrs_sort_mode.hip", "vrs_capi_sort_rank.hip",
+                                        "vrs_unique.hip", "vrs_unique_rows.hip", "vrs_capi_unique.hip", "vrs_sort_rank.hip", "vrs_sort_mode.hip", "vrs_capi_sort_rank.hip",
                                         "vrs_search.hip", "vrs_capi_search.hip", "vrs_bincount.hip", "vrs_capi_bincount.hip",
                                         "vrs_segreduce.hip", "vrs_capi_segreduce.hip",
                                         "vrs_scan.hip", "vrs_scan_pairs.hip", "vrs_capi_scan.hip",

@@ -103,6 +103,14 @@ VRS_RLE_COUNTS = 1
 VRS_UNIQUE_U32, VRS_UNIQUE_I32, VRS_UNIQUE_F32, VRS_UNIQUE_U64, VRS_UNIQUE_I64, VRS_UNIQUE_F64 = 0, 1, 2, 3, 4, 5
 VRS_UNIQUE_INVERSE, VRS_UNIQUE_COUNTS = 1, 2
 RLE_TILE = 4096
+VRS_UNIQUE_COLUMNS_SHIFT = 8
+
+
+def VRS_UNIQUE_COLUMNS(c: int) -> int:
+    """the columns per row of the row forms, for vrs_unique's key_type and vrs_run_length_encode's key_bytes (bits 8 and up)"""
+    return int(c) << VRS_UNIQUE_COLUMNS_SHIFT
+
+
 # the torch.sort drop-in's rank / restore kernels: dtypes (vrs_sort_dtype) and flags
 (VRS_SORT_INT8, VRS_SORT_UINT8, VRS_SORT_INT16, VRS_SORT_INT32, VRS_SORT_INT64, VRS_SORT_FLOAT16, VRS_SORT_BFLOAT16, VRS_SORT_FLOAT32,
  VRS_SORT_FLOAT64) = range(9)

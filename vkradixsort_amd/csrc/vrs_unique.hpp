@@ -97,6 +97,8 @@ struct RleArgs {
 
 // the encode (one pass over the keys, decoupled look-back across tiles) and, with out_counts, the counts from the offsets; n > 0
 hipError_t launch_rle(hipStream_t stream, const RleArgs &a);
+// counts[j] = offsets[j + 1] - offsets[j] for j < R (a.out_offsets, a.out_num_runs, a.out_counts; the grid from a.n)
+hipError_t launch_rle_counts(hipStream_t stream, const RleArgs &a);
 // vrs_unique: keys -> rank-mapped keys in `mapped`, iota payloads in `vals` (null: none); n > 0
 hipError_t launch_unique_map(hipStream_t stream, const void *keys, uint32_t n, int key_type, void *mapped, uint32_t *vals);
 

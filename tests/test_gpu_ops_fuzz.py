@@ -47,6 +47,13 @@ def test_the_committed_runs_of_the_newer_deck_pass(seed, count):
     assert fuzz.run(seed, count, "cuda:0", deck="newer") == count
 
 
+@pytest.mark.parametrize("seed,count", fuzz.COMMITTED_RUNS_THIRD)
+def test_the_committed_runs_of_the_third_deck_pass(seed, count):
+    """repeat_interleave, isin, mode and the dim= forms of unique / unique_consecutive between the other decks' ops, a deferred sort
+    pending in front of every second window: every output bit for bit against torch on the CPU and numpy."""
+    assert fuzz.run(seed, count, "cuda:0", deck="third") == count
+
+
 def test_a_kept_layout_meets_other_values_between_other_ops(capsys):
     """Three 1-D sorts of one element count above the pool-form minimum through vrs.sort (key + position pairs: the minimum of that kind)
     on the shared context: uniform, then so skewed that the regions kept from the first cannot fit, then uniform again, with vrs.unique

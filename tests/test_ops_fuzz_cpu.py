@@ -844,3 +844,477 @@ def test_a_swapped_pair_of_tied_indices_and_a_dropped_row_are_reported(newer_cas
     assert rows.shape[0] > 1 and fuzz.check(c, cpu, rows) == []
     lines = fuzz.check(c, cpu, rows[:-1])
     assert lines and lines[0].startswith("rows")
+
+
+# ==== the third deck ==============================================================================================================
+# repeat_interleave, isin, mode and the dim= forms of unique / unique_consecutive: the same claims for the committed run of deck "third".
+
+NEWER_DECK_SHA256 = "6b27afadb6e94739b9f0755aab7ebd232b140dcdd7dd7e1947c800bd86bbd772"  # json.dumps(list(cases(491, 256, deck="newer")), sort_keys=True)
+SEGMENT_TIERS = ("wave", "block", "global", "one_call")
+
+
+@pytest.fixture(scope="module")
+def third_cases():
+    return [c for seed, count in fuzz.COMMITTED_RUNS_THIRD for c in fuzz.cases(seed, count, deck="third")]
+
+
+def _third_takes(op: str, name: str) -> bool:
+    """_wrapper_takes for repeat_interleave, isin and mode: with small CPU tensors of the dtype, a wrapper that takes it gets as far as
+    refusing tensors that are not on a GPU; one that does not refuses the dtype first."""
+    x, index = torch.zeros(4, dtype=getattr(torch, name)), torch.zeros(4, dtype=torch.int64)
+    calls = {"repeat_interleave": lambda: vrs.repeat_interleave(x, index), "isin": lambda: vrs.isin(x, x), "mode": lambda: vrs.mode(x, 0)}
+    try:
+        calls[op]()
+    except vrs.VrsError as e:
+        return "on a GPU" in str(e)
+    except RuntimeError:
+        return False
+    raise AssertionError(f"{op} took CPU tensors")
+
+
+def accepted_third() -> dict:
+    """What the third deck's wrappers accept, by their own refusals (the dim= forms look at the device before the dtype: their refusal's
+    own list, as for the word forms)."""
+    return {**{op: {name for name in fuzz.TEN if _third_takes(op, name)} for op in ("repeat_interleave", "isin", "mode")},
+            "unique_dim": _refusal_dtypes(unique_mod._check_tensor), "unique_consecutive_dim": _refusal_dtypes(unique_mod._check_tensor)}
+
+
+def _own(cases, op=None):
+    return [c for c in cases if c["op"] in fuzz.THIRD_OPS and (op is None or c["op"] == op)]
+
+
+def _sizes_third(case):
+    return [_numel(case[k]) for k in ("shape", "test_shape") if k in case] + [case.get("total", 0) + case.get("extra", 0)]
+
+
+def _isin_promoted(case) -> str:
+    return fuzz._promoted_name(case["dtype"], case["test_dtype"])
+
+
+def classify_third(lib, case) -> dict:
+    """What a case of the third deck's ops runs, by the wrappers' own rules and the library's pure functions on the description alone:
+    {"form": (key bytes, pairs, form, n)} of the one-call sort inside, {"segment": (wide, tier, length)}, {"search": (dtype, tier, m, q)},
+    {"scan": (tier, runs)}, {"tiles": (row length, rows)}."""
+    t = fuzz.thresholds()
+    op, out = case["op"], {}
+    if op == "mode":
+        shape, n = case["shape"], _numel(case["shape"])
+        if shape:
+            length = shape[case["dim"] % len(shape)]
+            wide = fuzz.DTYPE_BYTES[case["dtype"]] == 8
+            out["tiles"] = (length, n // length)
+            if length > 1 and n == length:   # vrs_sort_keys_u32 / _u64 of the ranks
+                out["form"] = (8 if wide else 4, False, _form(lib, n, 8 if wide else 4, False), n)
+            elif length > 1:                 # vrs_sort_segments_u32 / _u64 of the ranks
+                out["segment"] = (wide, _segment_tier(lib, length, wide, False), length)
+    elif op == "isin":
+        m, q = _numel(case["test_shape"]), _numel(case["shape"])
+        name = _isin_promoted(case)
+        if m and q:
+            out["search"] = (name, _search_tier(lib, m, m, q, q, getattr(torch, name)), m, q)
+            if m > 1:  # sort_values of the test set: bare keys for the integers, key + position pairs for the floats
+                kb, pairs = (8 if fuzz.DTYPE_BYTES[name] == 8 else 4), name in fuzz.FLOATS
+                out["form"] = (kb, pairs, _form(lib, m, kb, pairs), m)
+    elif op == "repeat_interleave":
+        if case["form"] in ("one_arg", "tensor", "tensor_strided") and case["runs"]:
+            out["scan"] = (scan_mod.TIER_NAMES[t.scan_tier(1, case["runs"], 1, case["repeats_dtype"], "int64", "cumsum")], case["runs"])
+    else:
+        N, C, word = case["N"], case["C"], fuzz.DTYPE_BYTES[case["dtype"]]
+        if op == "unique_dim" and N > 1:  # one column: the word form's sort; more: a stable pair sort per 8 bytes of row
+            kb, pairs = (word, case["return_inverse"]) if C == 1 else (8 if (C * word) % 8 == 0 or word == 8 else 4, True)
+            out["form"] = (kb, pairs, _form(lib, N, kb, pairs), N)
+    return out
+
+
+@pytest.fixture(scope="module")
+def third_classes(lib, third_cases):
+    return [classify_third(lib, c) if c["op"] in fuzz.THIRD_OPS else {} for c in third_cases]
+
+
+def test_both_older_decks_streams_are_what_they_were_before_the_third_deck():
+    import hashlib
+    import json
+    assert hashlib.sha256(json.dumps(list(fuzz.cases(104, 256)), sort_keys=True).encode()).hexdigest() == FIRST_DECK_SHA256
+    assert hashlib.sha256(json.dumps(list(fuzz.cases(491, 256, deck="newer")), sort_keys=True).encode()).hexdigest() == NEWER_DECK_SHA256
+    assert fuzz.COMMITTED_RUNS == [(104, 256)] and fuzz.COMMITTED_RUNS_NEWER == [(491, 256)]
+    assert not set(fuzz.THIRD_OPS) & set(fuzz.NEWER_OPS) and not set(fuzz.THIRD_OPS) & set(fuzz.FIRST_OPS)
+    assert set(fuzz.OP_DTYPES) == set(fuzz.FIRST_OPS) | set(fuzz.NEWER_OPS) and set(fuzz.THIRD_OP_DTYPES) == set(fuzz.THIRD_OPS)
+
+
+def test_the_third_deck_is_deterministic_and_plain():
+    import json
+    for seed, count in fuzz.COMMITTED_RUNS_THIRD:
+        a, b = list(fuzz.cases(seed, count, deck="third")), list(fuzz.cases(seed, count, deck="third"))
+        assert a == b and len(a) == count and [c["index"] for c in a] == list(range(count))
+        assert json.loads(json.dumps(a)) == a
+        assert a[:40] != list(fuzz.cases(seed + 1000, 40, deck="third"))
+        assert all(c["deck"] == "third" for c in a)
+    assert len(fuzz.COMMITTED_RUNS_THIRD) == 1 and fuzz.COMMITTED_RUNS_THIRD[0][1] == 256
+    assert fuzz.replay_line(7, 3, "third").endswith("--deck third")
+
+
+def test_every_third_op_and_dtype_the_wrappers_accept_occurs(third_cases):
+    accepted = accepted_third()
+    assert fuzz.THIRD_OPS == ("repeat_interleave", "isin", "mode", "unique_dim", "unique_consecutive_dim")
+    assert {op: set(d) for op, d in fuzz.THIRD_OP_DTYPES.items()} == accepted
+    assert not _third_takes("isin", "bool") and not _third_takes("mode", "bool") and _third_takes("repeat_interleave", "bool")
+    seen = {(c["op"], c["dtype"]) for c in _own(third_cases)} | {("isin", c["test_dtype"]) for c in _own(third_cases, "isin")}
+    missing = {(op, dt) for op in fuzz.THIRD_OPS for dt in accepted[op]} - seen
+    assert not missing, sorted(missing)
+    isin = _own(third_cases, "isin")
+    for dt in accepted["isin"]:  # the nine dtypes on both sides
+        assert any(c["dtype"] == dt for c in isin) and any(c["test_dtype"] == dt for c in isin), dt
+    assert {(c["test_dtype"], c["dtype"]) for c in isin if c["variant"] == "mixed"} == {tuple(p[:2]) for p in fuzz.MIXED_PAIRS}
+    assert all(_isin_promoted(c) == p for c in isin if c["variant"] == "mixed" for p in [dict((tuple(q[:2]), q[2]) for q in fuzz.MIXED_PAIRS)[c["test_dtype"], c["dtype"]]])
+    assert {c["repeats_dtype"] for c in _own(third_cases, "repeat_interleave")} == {"int32", "int64"}
+
+
+def test_every_third_tier_and_form_occurs(lib, third_cases, third_classes):
+    assert {k["search"][1] for k in third_classes if "search" in k} == {"lds", "direct", "table", "indexed"}
+    segments = {k["segment"][:2] for k in third_classes if "segment" in k}
+    assert segments == {(w, t) for w in (False, True) for t in SEGMENT_TIERS}, sorted(segments)
+    grid = sorted({v for e in range(24) for v in (1 << e, (1 << e) + 1, 3 << e >> 1) if 1 < v <= fuzz.LARGE_ELEMENTS})
+    for op, kinds in (("mode", [(4, False), (8, False)]), ("isin", [(4, False), (4, True), (8, False), (8, True)]), ("unique_dim", [(4, True), (8, True)])):
+        seen = {k["form"][:3] for c, k in zip(third_cases, third_classes) if c["op"] == op and "form" in k}
+        for kb, pairs in kinds:  # every form of the one-call sort up to the cap, the pool form of bare 4-byte keys among them
+            reachable = {_form(lib, n, kb, pairs) for n in grid}
+            assert {f for b, p, f in seen if (b, p) == (kb, pairs)} >= reachable, (op, kb, pairs, sorted(seen))
+    assert "pool" in {_form(lib, n, 4, False) for n in grid}
+    assert {k["scan"][0] for k in third_classes if "scan" in k} >= {"tile", "three_launch"}
+
+
+def test_every_third_threshold_has_its_three_edges(third_cases, third_classes):
+    t = fuzz.thresholds()
+    low, tile = capi.ONE_CALL_MIN_KEYS_DEFAULT, capi.RLE_TILE
+
+    def edges(values, cut, what):
+        assert {cut - 1, cut, cut + 1} <= set(values), (what, cut, sorted(v for v in set(values) if abs(v - cut) < 3))
+
+    own = list(zip(third_cases, third_classes))
+    # mode: one row around the one-call sort's form cuts of either rank width, the pool minimum among them; many rows around the segmented
+    # sort's three cuts of either rank width (the third one, the one-call tier's, is one setting for both widths)
+    for kb in (4, 8):
+        for cut in t.form_cuts[kb, 0]:
+            edges([k["form"][3] for c, k in own if c["op"] == "mode" and "form" in k and k["form"][0] == kb], cut, f"mode, one row, {kb}-byte ranks")
+    assert t.pool_min in t.form_cuts[4, 0]
+    for wide in (False, True):
+        for cut in t.segment[wide, False][:2]:
+            edges([k["segment"][2] for c, k in own if "segment" in k and k["segment"][0] == wide], cut, f"mode, many rows, wide {wide}")
+    edges([k["segment"][2] for c, k in own if "segment" in k], t.segment_one_call_min, "mode, many rows, the one-call tier")
+    for kind in ("mode_pool_skewed", "mode_pool_uniform"):
+        edges([c["shape"][0] for c in third_cases if c["role"] == "large:" + kind], t.pool_min, kind)
+    tiles = [k["tiles"] for c, k in own if "tiles" in k]
+    for length in fuzz.MODE_SHORT:  # at least three full tiles of the run tables
+        assert any(L == length and rows * L >= 3 * tile for L, rows in tiles), length
+    assert {tile - 1, tile, tile + 1} <= {L for L, _ in tiles}
+    # isin: the search's three cuts for the promoted dtype, the one-call minimum and the sort's form cuts for the test set
+    searches = [k["search"] for c, k in own if "search" in k]
+    out4 = t.search["int32"][0]
+    assert {t.search[d][0] for d in fuzz.DTYPES} == {out4, t.search["int64"][0]}
+    edges([m for d, _, m, _ in searches if t.search[d][0] == out4], out4, "isin: the test set leaves LDS")
+    assert t.search["int64"][0] in [m for d, _, m, _ in searches if fuzz.DTYPE_BYTES[d] == 8]
+    edges([q for d, _, _, q in searches if fuzz.DTYPE_BYTES[d] == 1], t.search["int8"][1], "isin: the table's minimum of queries")
+    assert t.search["int16"][1] in [q for d, _, _, q in searches if fuzz.DTYPE_BYTES[d] == 2]
+    edges([q for d, _, _, q in searches if fuzz.DTYPE_BYTES[d] >= 4], t.search["int32"][2], "isin: the index's minimum of queries")
+    bare = [k["form"][3] for c, k in own if c["op"] == "isin" and "form" in k and k["form"][:2] == (4, False)]
+    for cut in t.form_cuts[4, 0]:
+        edges(bare, cut, "isin: the test set's sort of bare 4-byte keys")
+    edges(bare, low, "isin: the one-call minimum, bare keys")
+    edges([k["form"][3] for c, k in own if c["op"] == "isin" and "form" in k and k["form"][:2] != (4, False)], low, "isin: the one-call minimum, pairs or 8-byte keys")
+    # repeat_interleave: runs around the scan's cuts for repeats -> int64, totals around 1, 2 and 5 chunks
+    repeats = _own(third_cases, "repeat_interleave")
+    cuts = [c for c in t.scan_cuts("int32", "int64", "cumsum") if c and c < fuzz.SMALL_ELEMENTS // 2]
+    assert cuts == [c for c in t.scan_cuts("int64", "int64", "cumsum") if c and c < fuzz.SMALL_ELEMENTS // 2] == [t.scan_levels[0]]  # (the int64 output's tile)
+    for cut in cuts:
+        edges([c["runs"] for c in repeats if c["rep_class"] != "equal"], cut, "repeat_interleave: runs")
+        assert {c["repeats_dtype"] for c in repeats if c["rep_class"] != "equal" and abs(c["runs"] - cut) <= 1} == {"int32", "int64"}
+    for chunks in (1, 2, 5):
+        edges([c["total"] for c in repeats], chunks * fuzz.REPEAT_CHUNK, "repeat_interleave: total")
+    # unique(dim=) / unique_consecutive(dim=): N around the encode's tile, the one-call minimum and the pair sort's form cuts
+    for op in ("unique_dim", "unique_consecutive_dim"):
+        rows = [c["N"] for c in _own(third_cases, op)]
+        for cut in {tile, low, *t.form_cuts[4, 1], *t.form_cuts[8, 1]}:
+            edges(rows, cut, op)
+        assert max(rows) > tile + 1 and any(tile + 1 < n < low - 1 or low + 1 < n for n in rows)
+    sizes = [v for c in _own(third_cases) for v in _sizes_third(c)]
+    assert max(sizes) == fuzz.LARGE_ELEMENTS and 0 in sizes
+    small = sum(1 for c in third_cases if c["op"] not in fuzz.THIRD_OPS or max(_sizes_third(c)) <= fuzz.SMALL_ELEMENTS)
+    assert small >= 0.7 * len(third_cases)
+
+
+def test_every_third_class_of_argument_occurs(third_cases):
+    both = {False, True}
+    mode = _own(third_cases, "mode")
+    assert {c["values"] for c in mode if c["dtype"] in fuzz.FLOATS} >= set(fuzz.MODE_CLASSES)
+    assert {c["values"] for c in mode if c["dtype"] not in fuzz.FLOATS} >= set(fuzz.MODE_CLASSES[:-1])
+    assert {c["keepdim"] for c in mode} == both and {c["layout"]["kind"] for c in mode} == set(fuzz.LAYOUTS)
+    assert any(c["dim"] < 0 for c in mode) and {c["dim"] % len(c["shape"]) for c in mode if len(c["shape"]) == 3} == {0, 1, 2}
+    assert [] in [c["shape"] for c in mode] and {c["size"] for c in mode} == {"one_row", "many_rows", "short", "tile_len", "tiny", "large"}
+    isin = _own(third_cases, "isin")
+    assert {c["variant"] for c in isin} == set(fuzz.ISIN_VARIANTS)
+    assert {c["invert"] for c in isin} == both and {c["assume_unique"] for c in isin} == both
+    assert {c["share"] for c in isin} == set(fuzz.ISIN_SHARES) and {c["nans"] for c in isin} == set(fuzz.ISIN_NANS)
+    assert {c["signed_zero"] for c in isin if _isin_promoted(c) in fuzz.FLOATS} == both
+    assert {c["layout"]["kind"] for c in isin} == set(fuzz.LAYOUTS) and {c["test_layout"]["kind"] for c in isin} == set(fuzz.LAYOUTS)
+    assert any(c["shape"] == [] and c["variant"] != "number_elements" for c in isin) and any(_numel(c["shape"]) == 0 for c in isin)
+    assert any(_numel(c["test_shape"]) == 0 for c in isin) and any(len(c["test_shape"]) >= 2 and _numel(c["test_shape"]) > 1 for c in isin)
+    assert any(len(c["shape"]) >= 2 and _numel(c["shape"]) > 1 for c in isin)
+    repeats = _own(third_cases, "repeat_interleave")
+    assert {c["form"] for c in repeats} == set(fuzz.REPEAT_FORMS) and {c["rep_class"] for c in repeats} == set(fuzz.REPEAT_CLASSES) | {"equal"}
+    assert {c["output_size"] for c in repeats} == set(fuzz.OUTPUT_SIZES)
+    for form in ("one_arg", "tensor"):
+        assert {c["output_size"] for c in repeats if c["form"] == form} == set(fuzz.OUTPUT_SIZES), form
+    assert {c["repeats_layout"]["kind"] for c in repeats} == {"contiguous", "strided", "offset"}
+    with_input = [c for c in repeats if c["form"] != "one_arg"]
+    assert {c["dim"] is None for c in with_input} == both and any(c["dim"] is not None and c["dim"] < 0 for c in with_input)
+    assert {c["dim"] % len(c["shape"]) for c in with_input if c["dim"] is not None and len(c["shape"]) == 3} == {0, 1, 2}
+    assert {c["layout"]["kind"] for c in with_input} == set(fuzz.LAYOUTS)
+    assert any(c["total"] == 0 for c in repeats) and any(c["runs"] == 0 for c in repeats)
+    for op in ("unique_dim", "unique_consecutive_dim"):
+        rows = _own(third_cases, op)
+        assert {(c["return_inverse"], c["return_counts"]) for c in rows} == {(a, b) for a in both for b in both}, op
+        assert {c["C"] for c in rows} == set(fuzz.UNIQUE_COLUMNS) and {c["layout"]["kind"] for c in rows} == set(fuzz.LAYOUTS), op
+        assert {c["rows"] for c in rows if c["dtype"] in fuzz.FLOATS} >= set(fuzz.ROW_CLASSES), op
+        assert {c["rows"] for c in rows if c["dtype"] not in fuzz.FLOATS} >= set(fuzz.ROW_CLASSES[:-1]), op
+        assert {len(c["shape"]) for c in rows} == {2, 3} and {(len(c["shape"]), c["dim"] % len(c["shape"])) for c in rows} == {(2, 0), (2, 1), (3, 0), (3, 1), (3, 2)}, op
+        assert any(c["dim"] < 0 for c in rows), op
+        assert all(c["C"] * fuzz.DTYPE_BYTES[c["dtype"]] > 8 for c in rows if c["rows"] == "behind_top"), op
+    assert {c["stream"] for c in third_cases} == {"current", "second"}
+    assert all((c["stream"] == "second") == (c["window"] % 5 == 4) for c in third_cases)
+    assert {c["stream"] for c in _own(third_cases, "isin")} == {"current", "second"}
+
+
+def test_the_third_decks_large_minority_occurs(third_cases):
+    t = fuzz.thresholds()
+    large = [c for c in third_cases if c["role"].startswith("large:")]
+    assert [c["index"] for c in large] == [i for i in range(len(third_cases)) if i % fuzz.LARGE_EVERY == fuzz.LARGE_AT]
+    kinds = {}
+    for c in large:
+        kinds.setdefault(c["role"].split(":")[1], []).append(c)
+    assert set(kinds) == set(fuzz.LARGE_KINDS_THIRD) and len(set(fuzz.LARGE_KINDS_THIRD)) == 10
+    for kind in ("mode_pool_skewed", "mode_pool_uniform"):
+        assert all(c["op"] == "mode" and c["dtype"] in ("int32", "float32") and len(c["shape"]) == 1 and abs(c["shape"][0] - t.pool_min) <= 1 for c in kinds[kind])
+        assert {c["values"] for c in kinds[kind]} == {"thousand" if kind == "mode_pool_skewed" else "uniform"}
+    assert {c["dtype"] for c in kinds["mode_pool_skewed"]} == {"int32", "float32"}
+    assert all(sorted(c["shape"]) == [3, 1 << 20] and c["shape"][c["dim"]] == 3 for c in kinds["mode_rows_of_3"])
+    assert all(c["dtype"] == "int64" and c["shape"] == [1 << 22] for c in kinds["mode_int64_row"])
+    assert all(abs(_numel(c["test_shape"]) - t.pool_min) <= 1 and c["shape"] == [1 << 20] and fuzz.DTYPE_BYTES[c["dtype"]] == 4 for c in kinds["isin_pool"])
+    assert "int32" in {c["dtype"] for c in kinds["isin_pool"]}  # (bare keys: the pool form)
+    assert len({_numel(c["test_shape"]) for c in kinds["isin_pool"]}) >= 2
+    assert all(c["dtype"] == "int16" and c["shape"] == [1 << 23] and c["test_shape"] == [10_000] for c in kinds["isin_int16"])
+    assert all(c["runs"] == 1 << 10 and c["total"] == 1 << 23 for c in kinds["repeat_few_runs"])
+    assert all(c["runs"] == 1 << 22 and c["total"] == 1 << 23 for c in kinds["repeat_many_runs"])
+    assert all(c["shape"] == [1 << 21, 3] and c["dtype"] == "int32" and c["rows"] == "thousand" for c in kinds["unique_dim_large"])
+
+
+def test_every_third_window_has_its_neighbour_and_every_second_its_pending_sort(lib, third_cases):
+    windows = {}
+    for c in third_cases:
+        windows.setdefault(c["window"], []).append(c)
+    origins = set()
+    for w, group in windows.items():
+        assert len(group) == 4
+        old = [c for c in group if c["op"] not in fuzz.THIRD_OPS]
+        assert old and any(c["op"] in fuzz.THIRD_OPS for c in group), w
+        origins |= {"first" if c["op"] in fuzz.FIRST_OPS else "newer" for c in old}
+        first = group[0]
+        assert (first["role"] == "pending_sort") == (w % 2 == 0), w
+        if w % 2 == 0:
+            assert first["op"] in ("sort", "sort_values", "unique") and len(first["shape"]) == 1 and first["shape"][0] >= capi.ONE_CALL_MIN_KEYS_DEFAULT
+            assert "form" in classify(lib, first) and group[1]["op"] in fuzz.THIRD_OPS  # (the next op's settle_pending meets it)
+        else:
+            assert group[-1]["role"] == "neighbour"
+    assert origins == {"first", "newer"}
+    behind = {windows[w][1]["op"] for w in windows if w % 2 == 0}
+    assert behind == set(fuzz.THIRD_OPS), behind  # each of the five ops runs straight behind someone else's pending sort
+
+
+def test_no_third_case_leaves_an_ops_documented_domain(third_cases):
+    accepted = {**accepted_dtypes(), **accepted_third()}
+    for c in third_cases:
+        op = c["op"]
+        assert c["dtype"] in accepted[op], c
+        if op not in fuzz.THIRD_OPS:
+            continue
+        assert max(_sizes_third(c)) <= fuzz.LARGE_ELEMENTS < 1 << 32, c
+        nd = max(len(c["shape"]), 1)
+        if op == "mode":
+            assert -nd <= c["dim"] < nd and _numel(c["shape"]) > 0, c
+        elif op == "isin":
+            assert c["test_dtype"] in accepted[op] and getattr(torch, _isin_promoted(c)) in NINE, c
+            assert not (c["variant"] == "number_elements" and c["variant"] == "number_tests"), c
+        elif op == "repeat_interleave":
+            r = fuzz.make_repeats(c["runs"], c["rep_class"], c["total_target"], c["rep_seed"]) if c["rep_class"] != "equal" else fuzz.np.full(c["runs"], c["k"])
+            assert len(r) == c["runs"] and int(r.min(initial=0)) >= 0 and int(r.sum()) == c["total"] < 1 << 32, c
+            assert c["extra"] >= 0 and (c["extra"] > 0) == (c["output_size"] == "too_large"), c  # output_size is never below the true total
+            assert c["total_target"] is None or c["total"] == c["total_target"], c
+            assert c["repeats_dtype"] in ("int32", "int64") and c["total"] <= torch.iinfo(torch.int32).max, c
+            if c["form"] == "one_arg":
+                assert c["dtype"] == c["repeats_dtype"] and c["dim"] is None, c
+            else:
+                assert c["dim"] is None or -nd <= c["dim"] < nd, c
+                assert (_numel(c["shape"]) if c["dim"] is None else c["shape"][c["dim"]]) == c["runs"], c
+            assert not (c["output_size"] == "too_large" and (c["runs"] == 0 or c["form"] == "int")), c
+        else:
+            assert -nd <= c["dim"] < nd and c["shape"][c["dim"]] == c["N"] and _numel(c["shape"]) == c["N"] * c["C"], c
+            assert 1 <= c["C"] < 1 << 23 and c["N"] >= 1 and len(c["shape"]) in (2, 3), c
+
+
+# ---- torch's and numpy's own functions through check(): the third deck's references are right -------------------------------------------
+
+def _has_nan(cpu) -> bool:
+    x = cpu["x"]
+    return x.dtype.is_floating_point and bool(torch.isnan(x).any())
+
+
+# what is not handed to check(), by name (the first one leaves the values in: only the index is the reference's own)
+THIRD_SKIPS = {
+    "mode's index, where torch's choice is unspecified": lambda c, cpu: False,
+    "mode with NaNs": lambda c, cpu: c["op"] == "mode" and _has_nan(cpu),
+    "unique*_dim of floats with NaN or -0.0": lambda c, cpu: c["op"].endswith("_dim") and not fuzz.plain_values(cpu["x"]),
+    "a too-large output_size": lambda c, cpu: c["op"] == "repeat_interleave" and c["output_size"] == "too_large",
+}
+
+
+class _Independent:
+    """The third deck's ops by other means than the references take: torch.mode's values (the index is the reference's), numpy's isin and
+    repeat, torch.unique(dim=) / torch.unique_consecutive(dim=)."""
+
+    @staticmethod
+    def mode(x, dim, keepdim):
+        d = dim % max(x.dim(), 1)
+        index = fuzz.ref_mode(x, d)[1]
+        index = index if keepdim or not x.dim() else index.squeeze(d)
+        exact = x.double() if x.dtype.is_floating_point else x.long()
+        return (torch.mode(exact, dim, keepdim).values.to(x.dtype) if x.dim() else x.clone()), index
+
+    @staticmethod
+    def isin(elements, tests, assume_unique=False, invert=False):
+        common = torch.result_type(elements, tests)
+        up = torch.float32 if common in (torch.float16, torch.bfloat16) else common
+        e, t = (v.to(up) if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=up) for v in (elements, tests))
+        return torch.from_numpy(fuzz.np.asarray(fuzz.np.isin(e.contiguous().numpy(), t.contiguous().numpy(), invert=invert)))
+
+    @staticmethod
+    def repeat_interleave(x, repeats=None, dim=None, output_size=None):
+        np = fuzz.np
+        if repeats is None:
+            return torch.from_numpy(np.repeat(np.arange(x.numel()), x.numpy())).to(x.dtype)
+        r = repeats.reshape(-1).numpy() if isinstance(repeats, torch.Tensor) else repeats
+        r = int(r[0]) if not isinstance(r, int) and r.size == 1 else r
+        bits = fuzz.to_bits(x.view(torch.uint8) if x.dtype == torch.bool else x)
+        out = np.repeat(bits.reshape(-1) if dim is None else bits, r, axis=0 if dim is None else dim)
+        return fuzz.from_bits(out.reshape(-1), "uint8" if x.dtype == torch.bool else str(x.dtype).split(".")[1]).reshape(out.shape).view(x.dtype)
+
+    unique = staticmethod(lambda x, **kw: torch.unique(x, **kw))
+    unique_consecutive = staticmethod(lambda x, **kw: torch.unique_consecutive(x, **kw))
+
+
+def test_torchs_and_numpys_own_functions_pass_the_third_decks_checks(third_cases):
+    """Every case of the third deck's ops in the committed run below SMALL_ELEMENTS, but those THIRD_SKIPS names: the op by other means
+    (contiguous copies: this is about the references) handed to check() as if it were the library's result.  It reports nothing.  And the
+    conditions on the run: no case is without its numpy / torch reference, and at least half of the float cases of mode and of the two dim=
+    forms are plain, so that torch's own answer is compared as well."""
+    ran, skipped, plain, floats = {}, {}, {}, {}
+    for c in _own(third_cases):
+        if max(_sizes_third(c)) > THROUGH_TORCH_ELEMENTS:
+            continue
+        cpu, _ = fuzz.prepare(c, None)
+        op = c["op"]
+        if op != "isin" and c["dtype"] in fuzz.FLOATS and "x" in cpu and op != "repeat_interleave":
+            floats[op] = floats.get(op, 0) + 1
+            plain[op] = plain.get(op, 0) + (not _has_nan(cpu) if op == "mode" else fuzz.plain_values(cpu["x"]))
+        named = [name for name, applies in THIRD_SKIPS.items() if applies(c, cpu)]
+        if named:
+            skipped[named[0]] = skipped.get(named[0], 0) + 1
+            continue
+        result = fuzz.call_third(_Independent(), c, {k: v.contiguous() if isinstance(v, torch.Tensor) else v for k, v in cpu.items()})
+        assert fuzz.check(c, cpu, result) == [], c
+        ran[op] = ran.get(op, 0) + 1
+    assert set(ran) == set(fuzz.THIRD_OPS)
+    print(f"through torch / numpy: {sum(ran.values())} cases ran, skipped by name: {skipped}; plain float cases: {plain} of {floats}")
+    for op in ("mode", "unique_dim", "unique_consecutive_dim"):
+        assert 2 * plain[op] >= floats[op] > 0, (op, plain, floats)
+    assert sum(skipped.values()) * 4 <= sum(ran.values())
+
+
+# ---- one changed element: the third deck's references would notice --------------------------------------------------------------------
+
+def _first_case(cases, op, ok):
+    for c in _own(cases, op):
+        if max(_sizes_third(c)) <= 20_000:
+            cpu, _ = fuzz.prepare(c, None)
+            found = ok(c, cpu)
+            if found is not None and found is not False:
+                return c, cpu, found
+    raise AssertionError(f"no {op} case of the committed run fits")
+
+
+def _named(c, cpu, outputs, name):
+    lines = fuzz.check(c, cpu, tuple(outputs))
+    assert lines and lines[0].startswith(name), (c, name, lines)
+
+
+def test_one_changed_element_of_a_third_deck_output_is_reported_by_name(third_cases):
+    np = fuzz.np
+    # isin: a flipped bool
+    c, cpu, _ = _first_case(third_cases, "isin", lambda c, cpu: _numel(c["shape"]) > 5 and _numel(c["test_shape"]) > 0)
+    want = fuzz.ref_isin(cpu["elements"], cpu["tests"], c["invert"])
+    assert fuzz.check(c, cpu, want) == []
+    flipped = want.clone().reshape(-1)
+    flipped[5] = ~flipped[5]
+    _named(c, cpu, [flipped.reshape(want.shape)], "result")
+    # repeat_interleave: an index off by one
+    c, cpu, _ = _first_case(third_cases, "repeat_interleave", lambda c, cpu: c["form"] == "one_arg" and c["total"] > 3)
+    want = fuzz.ref_repeat_interleave(c, cpu)
+    assert fuzz.check(c, cpu, want) == []
+    off = want.clone()
+    off[want.numel() // 2] += 1
+    _named(c, cpu, [off], "out")
+
+    # mode: the index moved to an earlier occurrence; the value swapped for the other value of a tie
+    def tied_row(c, cpu):
+        x = cpu["x"]
+        if x.dim() == 0 or c["values"] not in ("alphabet", "row_edges") or c["dtype"] in fuzz.FLOATS:
+            return None
+        rows = x.movedim(c["dim"], -1).reshape(-1, x.shape[c["dim"]]).numpy()
+        for r in range(min(rows.shape[0], 300)):
+            values, counts = np.unique(rows[r], return_counts=True)
+            top = values[counts == counts.max()]
+            if top.size >= 2 and counts.max() >= 2:
+                return r, top[1], int(np.flatnonzero(rows[r] == top[1])[-1]), int(np.flatnonzero(rows[r] == top[0])[0])
+        return None
+
+    c, cpu, (row, other, other_at, earlier) = _first_case(third_cases, "mode", tied_row)
+    x = cpu["x"]
+    d = c["dim"] % x.dim()
+    values, indices = fuzz.ref_mode(x, d)
+    outputs = [values, indices] if c["keepdim"] else [values.squeeze(d), indices.squeeze(d)]
+    assert fuzz.check(c, cpu, tuple(outputs)) == []
+    flat_values, flat_indices = values.movedim(d, -1).reshape(-1).clone(), indices.movedim(d, -1).reshape(-1).clone()
+    back = lambda flat: flat.reshape(values.movedim(d, -1).shape).movedim(-1, d) if c["keepdim"] else flat.reshape(values.movedim(d, -1).shape).squeeze(-1)  # noqa: E731
+    moved = flat_indices.clone()
+    moved[row] = earlier  # (an occurrence of the same value, not the last)
+    assert earlier < int(flat_indices[row])
+    _named(c, cpu, [outputs[0], back(moved)], "indices")
+    swapped_values, swapped_indices = flat_values.clone(), flat_indices.clone()
+    swapped_values[row], swapped_indices[row] = int(other), other_at  # (as frequent, at its own last occurrence, but not the smallest)
+    _named(c, cpu, [back(swapped_values), back(swapped_indices)], "values")
+    # unique(dim=): two adjacent rows of the values swapped, one inverse entry changed, one count changed, the last row dropped
+    for op in ("unique_dim", "unique_consecutive_dim"):
+        c, cpu, _ = _first_case(third_cases, op, lambda c, cpu: c["return_inverse"] and c["return_counts"] and c["N"] > 8
+                                and fuzz.ref_unique_rows(cpu["x"], c["dim"] % 2 if len(c["shape"]) == 2 else c["dim"] % 3, op != "unique_dim")[0].shape[c["dim"]] > 2)
+        d = c["dim"] % len(c["shape"])
+        values, inverse, counts = fuzz.ref_unique_rows(cpu["x"], d, op != "unique_dim")
+        assert fuzz.check(c, cpu, (values, inverse, counts)) == []
+        rows = values.movedim(d, 0).clone()
+        rows[[0, 1]] = rows[[1, 0]]
+        _named(c, cpu, [rows.movedim(0, d), inverse, counts], "values")
+        changed = inverse.clone()
+        changed[3] = (changed[3] + 1) % values.shape[d]
+        _named(c, cpu, [values, changed, counts], "inverse")
+        changed = counts.clone()
+        changed[-1] += 1
+        _named(c, cpu, [values, inverse, changed], "counts")
+        _named(c, cpu, [values.narrow(d, 0, values.shape[d] - 1), inverse, counts], "values")
+        assert fuzz.check(c, cpu, (values, inverse))[0].startswith("2 outputs returned")  # the tuple's arity

@@ -9,7 +9,7 @@ with references written on torch's CPU functions and numpy alone.  It stops at t
 case index, the last eight descriptions, the first differing position and a replay line, and starts nothing more on the GPU.
    python tools/fuzz_ops.py SECONDS SEED            (soak: the same runner with a time budget)
    python tools/fuzz_ops.py 0 SEED --count N        (replay the first N cases of a seed)
-Two decks of ops, never folded into one (`--deck`, `cases(..., deck=)`, `run(..., deck=)`).  "first": sort, sort_values, argsort, sort_rows,
+Three decks of ops, never folded into one (`--deck`, `cases(..., deck=)`, `run(..., deck=)`).  "first": sort, sort_values, argsort, sort_rows,
 topk, unique, unique_consecutive, searchsorted, bucketize; its stream of descriptions is pinned by a hash in tests/test_ops_fuzz_cpu.py.
 "newer": the selections (kthvalue, median, nanmedian, quantile, nanquantile), the counts (bincount, histc, histogram), the reductions
 (segment_reduce, index_add, index_reduce, scatter_reduce), the scans (cumsum, cumprod, cummax, cummin) and the compactions (nonzero,
@@ -20,6 +20,13 @@ wherever the result is defined exactly; float sums, products and means come in t
 (small integers, +-1 factors, lengths capped so that every partial result is representable: == against torch) and "general" (random
 finite values against the same operation in float64, within (t + 1) u sum|x| for a sum of t terms, t u / (1 - t u) relative for a
 product, one u more for a mean's division, u the dtype's epsilon, t u < 0.1 kept by the generator).
+"third": repeat_interleave, isin, mode and the dim= forms of unique / unique_consecutive (as ops "unique_dim" / "unique_consecutive_dim"), in
+the newer deck's windows: a neighbour from the first or the newer deck's ops in every window, a pending sort in front of every second one.
+All of its outputs are defined exactly and held bit for bit: repeat_interleave and isin to torch's CPU functions, mode and the dim= forms
+to numpy restatements of their documented rules (mode: the smallest of the most frequent values, -0.0 and +0.0 one value, all NaNs one
+value, the largest, the index of the LAST occurrence, the value with that element's bits; rows: words by the IEEE total order, equal when
+bit-identical) and, where torch defines the same answer (NaN-free mode values; integer rows and float rows without NaN and -0.0), to
+torch.mode / torch.unique(dim=) / torch.unique_consecutive(dim=) as well.
 tools/fuzz_gpu.py covers the raw key and pair sorts on a context of its own."""
 from __future__ import annotations
 
@@ -50,7 +57,12 @@ OP_DTYPES.update({"kthvalue": DTYPES, "median": DTYPES, "nanmedian": DTYPES, "qu
                   "segment_reduce": SIX, "index_add": SIX, "index_reduce": SIX, "scatter_reduce": SIX,
                   "cumsum": TEN, "cumprod": TEN, "cummax": TEN, "cummin": TEN,
                   "nonzero": TEN, "argwhere": TEN, "count_nonzero": TEN, "masked_select": TEN, "masked_scatter": TEN, "mask_index": TEN, "mask_index_put": TEN})
-NEWER_OPS = tuple(op for op in OP_DTYPES if op not in FIRST_OPS)
+NEWER_OPS = tuple(op for op in OP_DTYPES if op not in FIRST_OPS)  # (OP_DTYPES ends here: the first and the newer deck's ops, nothing joins it)
+# the third deck's ops; the dim= forms of unique / unique_consecutive under names of their own (the first deck's entries stay what they are)
+THIRD_OPS = ("repeat_interleave", "isin", "mode", "unique_dim", "unique_consecutive_dim")
+# what the third deck's wrappers accept: a table of its own, so that OP_DTYPES and NEWER_OPS stay what the two older decks and their tests read
+THIRD_OP_DTYPES = {"repeat_interleave": TEN, "isin": DTYPES, "mode": DTYPES, "unique_dim": KEY3264, "unique_consecutive_dim": KEY3264}
+THIRD_OP_TURNS = {"repeat_interleave": 5, "isin": 5, "mode": 6, "unique_dim": 4, "unique_consecutive_dim": 3}  # turns per round of the third deck's op deck
 OP_WEIGHT = {"searchsorted": 3, "bucketize": 2, "topk": 4, "sort_rows": 3, "unique": 2, "unique_consecutive": 2}  # (turns per round of the op x dtype deck: one unless named)
 CONTIGUOUS_ONLY = ("sort_rows", "topk", "unique", "unique_consecutive")  # these refuse a non-contiguous tensor
 LAYOUTS = ["contiguous", "transposed", "strided", "offset", "expanded"]
@@ -70,6 +82,7 @@ PENDING_BYTES_CAP = 1 << 30
 # (seed, count) of the runs tests/test_gpu_ops_fuzz.py makes; tests/test_ops_fuzz_cpu.py holds them to what the generator claims to reach
 COMMITTED_RUNS = [(104, 256)]
 COMMITTED_RUNS_NEWER = [(491, 256)]  # the same for the newer deck
+COMMITTED_RUNS_THIRD = [(7, 256)]    # and for the third
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -549,10 +562,11 @@ class _Gen:
 def cases(seed: int, count: int, window: int = 4, deck: str = "first"):
     """`count` case descriptions of `seed`: plain dicts of numbers, strings and lists.  The same everywhere; needs no device.
     deck "first": sort, topk, unique and the searches; "newer": the selections, counts, reductions, scans and compactions, every window with
-    a neighbour from the first deck's ops."""
-    if deck not in ("first", "newer"):
+    a neighbour from the first deck's ops; "third": repeat_interleave, isin, mode and unique / unique_consecutive along a dim, every window
+    with a neighbour from the first or the newer deck's ops."""
+    if deck not in ("first", "newer", "third"):
         raise ValueError(f"unknown deck {deck!r}")
-    return iter((_Gen if deck == "first" else _GenNewer)(seed, count, window))
+    return iter({"first": _Gen, "newer": _GenNewer, "third": _GenThird}[deck](seed, count, window))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -1199,6 +1213,10 @@ class _GenNewer(_Gen):
             return self._pending_sort()
         if window % 2 == 1 and at == self.window - 1:
             return self._neighbour()
+        return self._regular()
+
+    def _regular(self) -> list:
+        """The next (op, dtype) of the newer ops' deck as a case."""
         op, dtype = self.new_op_dtype.draw()
         if op in SELECT_OPS:
             case = self._select(op, dtype)
@@ -1792,6 +1810,668 @@ def check_newer(case: dict, cpu: dict, got: list) -> list:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# the third deck: repeat_interleave, isin, mode and the dim= forms of unique / unique_consecutive
+
+MODE_CLASSES = ["alphabet", "constant", "distinct", "hot", "row_edges", "specials"]  # (specials: floats; NaNs of several payloads, both zeros)
+MODE_SHORT = [1, 2, 3, 63, 64, 65]           # row lengths given enough rows for three full tiles of the run tables and more
+ISIN_VARIANTS = ["same", "same", "same", "mixed", "mixed", "mixed", "number_elements", "number_tests"]
+ISIN_SHARES = ["none", "half", "all"]        # about which share of the elements is a member
+ISIN_NANS = ["none", "elements", "tests", "both"]
+REPEAT_FORMS = ["one_arg", "one_arg", "tensor", "tensor", "tensor", "tensor_strided", "zero_d", "one_element", "int"]
+REPEAT_CLASSES = ["uniform_small", "mostly_zeros", "giant", "ones", "zeros", "zero_ends"]
+OUTPUT_SIZES = ["absent", "exact", "too_large"]
+REPEAT_CHUNK = 4096                          # the identity search writes its output in chunks of this many (vrs_search.hip)
+UNIQUE_COLUMNS = [1, 2, 3, 4, 5, 9]
+UNIQUE_REST = {1: [1, 1], 2: [2, 1], 3: [1, 3], 4: [2, 2], 5: [5, 1], 9: [3, 3]}  # the two trailing sizes of a 3-D shape with so many columns
+ROW_CLASSES = ["few", "equal", "distinct", "sorted", "last_column", "behind_top", "specials"]  # (specials: floats; NaN and -0.0 columns)
+# turns per round: once the last, whose reference, torch.unique(dim=) of 2^21 rows on the CPU, takes seconds; twice the others;
+# (three times a round what has three edges to draw)
+LARGE_KINDS_THIRD = (3 * ["mode_pool_skewed", "mode_pool_uniform", "mode_segment_one_call", "isin_pool"]
+                     + 2 * ["mode_rows_of_3", "mode_int64_row", "isin_int16", "repeat_few_runs", "repeat_many_runs"] + ["unique_dim_large"])
+
+
+def _wide(dtype: str) -> bool:
+    return DTYPE_BYTES[dtype] == 8
+
+
+def _promoted_name(a: str, b: str) -> str:
+    import torch
+    return str(torch.result_type(torch.empty(0, dtype=torch_dtype(a)), torch.empty(0, dtype=torch_dtype(b)))).split(".")[1]
+
+
+def make_repeats(runs: int, cls: str, total, seed: int):
+    """`runs` non-negative int64 repeats of class `cls` (REPEAT_CLASSES); total: their sum, where the class leaves it open (None: as drawn)."""
+    rng = np.random.Generator(np.random.PCG64(seed + 17))
+    if cls == "ones":
+        return np.ones(runs, dtype=np.int64)
+    if cls == "zeros" or runs == 0:
+        return np.zeros(runs, dtype=np.int64)
+    mean = max(1, -(-(total if total is not None else 3 * runs) // runs))
+    if cls == "uniform_small":
+        r = rng.integers(0, 2 * mean + 1, size=runs)
+    elif cls == "mostly_zeros":
+        r = np.where(rng.random(runs) < 0.9, 0, rng.integers(0, 20 * mean + 1, size=runs))
+    elif cls == "giant":
+        r = rng.integers(0, 2, size=runs)
+        r[int(rng.integers(runs))] = (total if total is not None else 20 * runs)
+    else:  # zero_ends
+        r = rng.integers(0, 2 * mean + 1, size=runs)
+    r = r.astype(np.int64)
+    ends = max(1, runs // 8) if cls == "zero_ends" and runs >= 3 else 0
+    if ends:
+        r[:ends] = 0
+        r[-ends:] = 0
+    if total is not None:  # (what is missing goes to the middle run; what is too much is cut off the end)
+        r[runs // 2] += max(0, total - int(r.sum()))
+        c = np.minimum(np.cumsum(r), total)
+        r = np.diff(c, prepend=0)
+    return r
+
+
+class _GenThird(_GenNewer):
+    """The third deck, in the newer deck's window structure.  Window w of four holds: w even, a pending 1-D sort / sort_values / unique of the
+    one-call minimum or more first; w odd, a neighbour last, from the first deck's ops and the newer deck's in turn; case i with
+    i % LARGE_EVERY == LARGE_AT is of the large minority; every other case is the next op of the third deck's op deck.  An op draws its
+    size plan first -- one deck per op, every edge of every cut one item of it -- and then a dtype that the plan's item allows."""
+
+    def __init__(self, seed: int, count: int, window: int):
+        super().__init__(seed, count, window)
+        rng = self.rng
+        self.third_op = _Deck(rng, [op for op in THIRD_OPS for _ in range(THIRD_OP_TURNS[op])])
+        self.third_dtype = {op: _Deck(rng, THIRD_OP_DTYPES[op]) for op in THIRD_OPS}
+        self.large_third = _Deck(rng, LARGE_KINDS_THIRD)
+        self.third_mixed = _Deck(rng, MIXED_PAIRS)
+
+    def _third_done(self, case: dict, role: str = "third") -> list:
+        case.update(deck="third", role=role, data_seed=self._seed())
+        return [case]
+
+    def _dtype_of(self, op: str, ok=None) -> str:
+        return self.third_dtype[op].draw(ok)
+
+    @staticmethod
+    def _edges(cuts) -> list:
+        return [c + d for c in sorted(set(cuts)) for d in (-1, 0, 1)]
+
+    def _exact_shape(self, n: int) -> list:
+        """A 1-D to 3-D shape of exactly n elements."""
+        rng = self.rng
+        kind = int(rng.integers(4))
+        if kind == 0 and n % 2 == 0 and n:
+            return [2, n // 2]
+        return [[n], [n], [1, n], [n, 1, 1]][kind]
+
+    # -- mode -------------------------------------------------------------------------------------------------------------------
+    def _mode(self) -> dict:
+        rng, t = self.rng, self.t
+        tile = t.capi.RLE_TILE  # (kModeTile of vrs_sort_mode.hip: the same 4096, and the constant the package exports)
+        cap = SMALL_ELEMENTS
+        plan = ([("one_row", kb, L) for kb in (4, 8) for L in self._edges(c for c in t.form_cuts[kb, 0] if c < cap) + [None]]
+                + [("many_rows", 8 if w else 4, L) for w in (False, True) for L in self._edges(t.segment[w, False][:2]) + [None]]
+                + [("short", 0, L) for L in MODE_SHORT] + [("tile_len", 0, tile + d) for d in (-1, 0, 1)] + [("tiny", 0, i) for i in range(2)])
+        kind, kb, L = self._pick("mode_plan", plan)
+        dtype = self._dtype_of("mode", None if not kb else (lambda d: _wide(d) == (kb == 8)))
+        if kind == "one_row":
+            L = L or int(rng.integers(2, cap + 1))
+            shape, dim = self._shape_with(1, L)
+        elif kind == "many_rows":
+            L = L or int(rng.integers(2, 1000))
+            shape, dim = self._shape_with(int(rng.integers(2, max(3, min(cap // L, 2000) + 1))), L)
+        elif kind == "short":
+            shape, dim = self._shape_with(-(-3 * tile // L) + int(rng.integers(1, 200)), L)
+        elif kind == "tile_len":
+            shape, dim = self._shape_with(int(rng.integers(1, 9)), L)
+        else:
+            shape, dim = ([], 0) if L == 0 else [([1], 0), ([2, 1], 1), ([1, 3], 0), ([4, 1, 2], 1)][int(rng.integers(4))]
+        if shape and rng.integers(2):
+            dim -= len(shape)
+        classes = MODE_CLASSES if dtype in FLOATS else MODE_CLASSES[:-1]
+        return {"op": "mode", "dtype": dtype, "shape": shape, "dim": dim, "keepdim": self._pick("keepdim", [False, True]), "layout": self._layout(shape),
+                "values": self._pick("mode_class_" + str(dtype in FLOATS), classes), "size": kind}
+
+    # -- isin -------------------------------------------------------------------------------------------------------------------
+    def _isin(self) -> dict:
+        rng, t = self.rng, self.t
+        low = t.capi.ONE_CALL_MIN_KEYS_DEFAULT
+        narrow, cuts4 = (lambda d: not _wide(d)), [c for c in t.form_cuts[4, 0] if c < SMALL_ELEMENTS and c != low]
+        bare4 = lambda d: not _wide(d) and d not in FLOATS  # noqa: E731  (the test set's sort is one of bare 4-byte keys)
+        plan = ([("out", d, narrow) for d in (-1, 0, 1)] + [("out", 0, _wide)]
+                + [("table", d, lambda n: DTYPE_BYTES[n] == 1) for d in (-1, 0, 1)] + [("table", 0, lambda n: DTYPE_BYTES[n] == 2)]
+                + [("index", d, lambda n: DTYPE_BYTES[n] >= 4) for d in (-1, 0, 1)]
+                + [("cut", m, bare4) for m in self._edges(cuts4)] + [("cut", m, bare4) for m in self._edges([low])]
+                + [("cut", m, ok) for ok in ((lambda n: n == "int64"), (lambda n: n == "float64"), (lambda n: n in FLOATS and not _wide(n))) for m in self._edges([low])]
+                + [("lds", 0, None), ("lds", 0, None), ("few", 0, None), ("empty_elements", 0, None), ("empty_tests", 0, None), ("zero_d", 0, None)])
+        variant = self._pick("isin_variant", ISIN_VARIANTS)
+        if "isin_plan" not in self.named:
+            self.named["isin_plan"] = _Deck(rng, plan)
+
+        def fits(item):  # (a number as elements is one query, a number as the test set one test element: the sizes that are about neither)
+            if variant == "mixed":
+                return any(item[2] is None or item[2](p[2]) for p in MIXED_PAIRS)
+            if variant == "number_elements":
+                return item[0] in ("out", "cut", "lds", "few")
+            return variant == "same" or item[0] in ("lds", "few", "zero_d")
+
+        kind, arg, ok = self.named["isin_plan"].draw(fits)
+        ok = ok or (lambda n: True)
+        if variant == "mixed":
+            test_dtype, dtype, common = self.third_mixed.draw(lambda p: ok(p[2]))
+        else:
+            dtype = test_dtype = common = self._dtype_of("isin", ok)
+        out, table, index = t.search[common]
+        q = int(rng.integers(1, 3000))
+        if kind == "out":
+            m, q = out + arg, int(rng.integers(1, 200))
+        elif kind == "table":
+            m, q = int(rng.integers(out, 2 * out)), table + arg
+        elif kind == "index":
+            m, q = int(rng.integers(out, 2 * out)), index + arg
+        elif kind == "cut":
+            m = arg
+        elif kind == "lds":
+            m = int(rng.integers(2, out - 1))
+        else:
+            m, q = int(rng.integers(1, 65)), int(rng.integers(1, 65))
+        shape = [] if kind == "zero_d" else [0] if kind == "empty_elements" else self._exact_shape(q)
+        test_shape = [[0], [2, 0]][int(rng.integers(2))] if kind == "empty_tests" else self._exact_shape(m)
+        case = {"op": "isin", "dtype": dtype, "test_dtype": test_dtype, "variant": variant, "shape": shape, "layout": self._layout(shape),
+                "test_shape": test_shape, "test_layout": self._layout(test_shape), "invert": self._pick("invert", [False, True]),
+                "assume_unique": self._pick("assume_unique", [False, False, True]), "share": self._pick("isin_share", ISIN_SHARES),
+                "dist": self._dist(dtype), "test_dist": self._dist(test_dtype), "size": kind,
+                "nans": self._pick("isin_nans", ISIN_NANS) if common in FLOATS else "none", "signed_zero": common in FLOATS and bool(rng.integers(2))}
+        if variant == "number_elements":
+            case.update(shape=[], layout={"kind": "contiguous"})
+        elif variant == "number_tests":
+            case.update(test_shape=[], test_layout={"kind": "contiguous"})
+        return case
+
+    # -- repeat_interleave --------------------------------------------------------------------------------------------------------
+    def _repeat(self) -> dict:
+        rng, t = self.rng, self.t
+        form = self._pick("repeat_form", REPEAT_FORMS)
+        rdt = self._pick("repeats_dtype", ["int32", "int64"])
+        how = self._pick("output_size", OUTPUT_SIZES)
+        case = {"op": "repeat_interleave", "form": form, "repeats_dtype": rdt, "repeats_layout": {"kind": "contiguous"}, "rep_seed": self._seed()}
+        if form in ("one_arg", "tensor", "tensor_strided"):
+            cuts = [c for c in t.scan_cuts(rdt, "int64", "cumsum") if c and c < SMALL_ELEMENTS // 2]
+            plan = [("runs", m) for m in self._edges(cuts)] + [("total", v) for v in self._edges(k * REPEAT_CHUNK for k in (1, 2, 5))] + [("free", 0), ("free", 0), ("empty", 0)]
+            cls = self._pick("repeat_class", REPEAT_CLASSES)
+            if "repeat_plan" not in self.named:  # (one plan for both dtypes of repeats: the scan's cuts are those of its int64 output)
+                self.named["repeat_plan"] = _Deck(rng, plan)
+            kind, arg = self.named["repeat_plan"].draw(lambda item: item[0] != "total" or cls != "zeros")
+            if kind == "empty":
+                runs, total = 0, None
+            elif kind == "runs":
+                runs, total = arg, None if cls in ("ones", "zeros") else int(rng.integers(arg, 4 * arg))
+            elif kind == "total":
+                runs, total = (arg if cls == "ones" else int(rng.integers(3, arg))), arg
+            else:
+                runs = int(rng.integers(0, 3)) if rng.integers(4) == 0 else int(rng.integers(3, 3000))
+                total = None if cls in ("ones", "zeros") or runs == 0 else int(rng.integers(runs, 4 * runs + 2))
+            true_total = int(make_repeats(runs, cls, total, case["rep_seed"]).sum())
+            case.update(runs=runs, rep_class=cls, total_target=total, total=true_total, size=kind)
+            if form == "tensor_strided":
+                case["repeats_layout"] = {"kind": "strided", "step": int(rng.integers(2, 4))} if self._pick("repeats_layout", [True, False]) else {"kind": "offset", "by": int(rng.integers(1, 4))}
+        else:
+            runs, k = int(rng.integers(1, 3000)), int(rng.integers(0, 5))
+            case.update(runs=runs, rep_class="equal", k=k, total_target=None, total=runs * k, size="free")
+            if form == "int" and how == "too_large":
+                how = "exact"  # (a Python int's total is known to the wrapper: another output_size is refused, as torch refuses it)
+        if case["runs"] == 0 and how == "too_large":
+            how = "exact"  # (no last element to repeat)
+        case.update(output_size=how, extra=int(rng.integers(1, 100)) if how == "too_large" else 0)
+        if form == "one_arg":
+            case.update(dtype=rdt, shape=[case["runs"]], dim=None, layout={"kind": "contiguous"})
+            return case
+        dtype = self._dtype_of("repeat_interleave")
+        runs = case["runs"]
+        width = max(1, min(4, SMALL_ELEMENTS // max(case["total"] + case["extra"], runs, 1)))
+        other = [[], [int(rng.integers(1, width + 1))], [2, width // 2] if width >= 4 else [1, 1]][self._pick("repeat_other", [0, 1, 2, 2])]
+        if self._pick("repeat_dim_none", [True, False, False]):
+            a = 2 if runs % 2 == 0 and runs and rng.integers(2) else 1
+            shape, dim = ([a, runs // a] if a == 2 else [runs]), None  # (the flattened input: runs elements)
+        else:
+            dim = self._pick("repeat_dim3", [0, 1, 2]) if len(other) == 2 else int(rng.integers(len(other) + 1))
+            shape = other[:dim] + [runs] + other[dim:]
+            dim = dim - len(shape) if rng.integers(2) else dim
+        case.update(dtype=dtype, shape=shape, dim=dim, layout=self._layout(shape), dist=self._value_dist(dtype))
+        return case
+
+    # -- unique(dim=) and unique_consecutive(dim=) ----------------------------------------------------------------------------------
+    def _unique_dim(self, op: str, N=None, C=None, dtype=None, rows=None) -> dict:
+        rng, t = self.rng, self.t
+        dtype = dtype or self._dtype_of(op)
+        cuts = {t.capi.RLE_TILE, t.capi.ONE_CALL_MIN_KEYS_DEFAULT, *t.form_cuts[4, 1], *t.form_cuts[8, 1]}
+        classes = ROW_CLASSES if dtype in FLOATS else ROW_CLASSES[:-1]
+        rows = rows or self._pick(f"rows_{op}_{dtype in FLOATS}", classes)
+        C = C or self._pick("columns_" + op, UNIQUE_COLUMNS)
+        if rows == "behind_top" and C * DTYPE_BYTES[dtype] <= 8:
+            C = [3, 4, 5, 9][int(rng.integers(4))]  # (something behind the first 8 bytes)
+        if N is None:
+            N = self._pick("rows_plan_" + op, self._edges(c for c in cuts if c < SMALL_ELEMENTS // 9) + [None, None, "tiny", "above"])
+            if N is None:
+                N = int(rng.integers(2, 3000))
+            elif N == "tiny":
+                N = int(rng.integers(1, 3))
+            elif N == "above":
+                N = int(rng.integers(t.capi.RLE_TILE + 2, min(20000, SMALL_ELEMENTS // C)))
+        rest = [C] if self._pick("unique_nd", [2, 3]) == 2 else UNIQUE_REST[C]
+        dim = int(rng.integers(len(rest) + 1))
+        shape = rest[:dim] + [N] + rest[dim:]
+        inverse, counts = self.flags4.draw()
+        return {"op": op, "dtype": dtype, "shape": shape, "dim": dim - len(shape) if rng.integers(2) else dim, "N": N, "C": C,
+                "layout": self._layout(shape), "return_inverse": inverse, "return_counts": counts, "rows": rows}
+
+    # -- the large minority -----------------------------------------------------------------------------------------------------
+    def _large_third(self) -> list:
+        rng, t = self.rng, self.t
+        kind = self.large_third.draw()
+        plain = {"kind": "contiguous"}
+        if kind in ("mode_pool_skewed", "mode_pool_uniform"):
+            n = t.pool_min + self._pick(kind + "_edge", [-1, 0, 1])
+            case = {"op": "mode", "dtype": self._turn(kind, ["int32", "float32"]), "shape": [n], "dim": 0, "keepdim": False, "layout": self._layout([n]),
+                    "values": "thousand" if kind == "mode_pool_skewed" else "uniform", "size": "large"}
+        elif kind == "mode_rows_of_3":
+            dtype = self._dtype_of("mode")
+            shape, dim = (([1 << 20, 3], -1) if rng.integers(2) else ([3, 1 << 20], 0))
+            case = {"op": "mode", "dtype": dtype, "shape": shape, "dim": dim, "keepdim": bool(rng.integers(2)), "layout": plain, "values": "alphabet", "size": "large"}
+        elif kind == "mode_int64_row":
+            case = {"op": "mode", "dtype": "int64", "shape": [1 << 22], "dim": -1, "keepdim": False, "layout": plain,
+                    "values": self._turn(kind, ["thousand", "hot", "uniform"]), "size": "large"}
+        elif kind == "mode_segment_one_call":
+            wide = self._turn(kind, [False, True])
+            length = t.segment[wide, False][2] + self._pick(kind + "_edge", [-1, 0, 1])
+            dtype = self._dtype_of("mode", lambda d: _wide(d) == wide)
+            shape, dim = (([2, length], 1) if rng.integers(2) else ([length, 2], 0))
+            case = {"op": "mode", "dtype": dtype, "shape": shape, "dim": dim, "keepdim": False, "layout": plain,
+                    "values": self._pick("mode_class_large", ["alphabet", "hot", "thousand", "row_edges"]), "size": "large"}
+        elif kind == "isin_pool":
+            m = t.pool_min + self._pick("isin_pool_edge", [-1, 0, 1])
+            dtype = self._turn(kind, ["int32", "int32", "int32", "float32"])  # (bare keys: the pool form; float32's test set sorts as pairs)
+            case = {"op": "isin", "dtype": dtype, "test_dtype": dtype, "variant": "same", "shape": [1 << 20], "layout": plain, "test_shape": [m], "test_layout": plain,
+                    "invert": bool(rng.integers(2)), "assume_unique": False, "share": "half", "dist": "uniform", "test_dist": "uniform", "size": "large",
+                    "nans": "none", "signed_zero": False}
+        elif kind == "isin_int16":
+            case = {"op": "isin", "dtype": "int16", "test_dtype": "int16", "variant": "same", "shape": [LARGE_ELEMENTS], "layout": plain, "test_shape": [10_000],
+                    "test_layout": plain, "invert": bool(rng.integers(2)), "assume_unique": False, "share": "none", "dist": "uniform", "test_dist": "uniform",
+                    "size": "large", "nans": "none", "signed_zero": False}
+        elif kind in ("repeat_few_runs", "repeat_many_runs"):
+            runs = 1 << 10 if kind == "repeat_few_runs" else 1 << 22
+            rdt = self._turn("large_repeats_dtype", ["int64", "int32"])
+            case = {"op": "repeat_interleave", "form": self._turn(kind, ["tensor", "one_arg"]), "repeats_dtype": rdt, "repeats_layout": plain, "rep_seed": self._seed(),
+                    "runs": runs, "rep_class": self._turn(kind + "_class", ["uniform_small", "mostly_zeros", "zero_ends"]), "total_target": LARGE_ELEMENTS,
+                    "total": LARGE_ELEMENTS, "size": "large", "output_size": self._turn(kind + "_size", ["exact", "absent"]), "extra": 0}
+            if case["form"] == "one_arg":
+                case.update(dtype=rdt, shape=[runs], dim=None, layout=plain)
+            else:
+                dtype = self._dtype_of("repeat_interleave", lambda d: DTYPE_BYTES[d] <= 4)
+                case.update(dtype=dtype, shape=[runs], dim=0, layout=plain, dist=self._value_dist(dtype))
+        else:
+            case = self._unique_dim("unique_dim", N=1 << 21, C=3, dtype="int32", rows="thousand")
+            case.update(shape=[1 << 21, 3], dim=0, layout=plain)
+        return self._third_done(case, "large:" + kind)
+
+    def _next(self) -> list:
+        window, at = divmod(self._index, self.window)
+        if self._index % LARGE_EVERY == LARGE_AT:
+            return self._large_third()
+        if window % 2 == 0 and at == 0:
+            case = self._pending_sort()[0]
+        elif window % 2 == 1 and at == self.window - 1:
+            case = (self._neighbour() if self._turn("neighbour_from", ["first", "newer"]) == "first" else self._regular())[0]
+            case["role"] = "neighbour"
+        else:
+            op = self.third_op.draw()
+            case = {"mode": self._mode, "isin": self._isin, "repeat_interleave": self._repeat}[op]() if not op.startswith("unique") else self._unique_dim(op)
+            return self._third_done(case)
+        case["deck"] = "third"
+        return [case]
+
+
+# -- the third deck's inputs (torch on the CPU and numpy; nothing of the library) ------------------------------------------------------
+
+def _finite_bits(rng, name: str, count):
+    """`count` random bit patterns of the dtype (a shape or a number), finite where it is a float."""
+    nbytes = DTYPE_BYTES[name]
+    ut = _BITS[nbytes]
+    b = rng.integers(0, 1 << (8 * nbytes), size=count, dtype=ut)
+    if name in FLOATS:
+        em = ut(_EXPONENT[name][0])
+        b = np.where((b & em) == em, b & ~ut(int(em) & -int(em)), b).astype(ut)
+    return b
+
+
+def _numbers_as_bits(numbers, name: str):
+    """Small integers (a numpy array) as the dtype's bit patterns."""
+    import torch
+    return to_bits(torch.from_numpy(np.ascontiguousarray(numbers, dtype=np.int64)).to(torch_dtype(name)))
+
+
+def _special_pool(name: str):
+    """NaNs of three payloads and both signs, both zeros, and a few numbers: the values of the "specials" classes, as bit patterns."""
+    em, mant = _EXPONENT[name]
+    sign, quiet = 1 << (8 * DTYPE_BYTES[name] - 1), 1 << (mant - 1)
+    ut = _BITS[DTYPE_BYTES[name]]
+    return np.concatenate((np.array([em | quiet, em | quiet | 1, sign | em | quiet | 2, 0, sign], dtype=ut), _numbers_as_bits(np.array([1, -1, 2]), name)))
+
+
+def _row_permuted(rng, a):
+    return rng.permuted(a, axis=1) if a.shape[1] > 1 else a
+
+
+def mode_values(name: str, shape, dim: int, cls: str, seed: int):
+    """A contiguous CPU tensor of `shape` whose rows along `dim` are of class `cls` (MODE_CLASSES, or "thousand" / "uniform" of the large kinds)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    shape = list(shape)
+    ut = _BITS[DTYPE_BYTES[name]]
+    if not shape:
+        return from_bits(_finite_bits(rng, name, 1), name).reshape(())
+    dim %= len(shape)
+    L = shape[dim]
+    moved = shape[:dim] + shape[dim + 1:] + [L]
+    R = _numel(moved) // max(L, 1)
+    if cls == "alphabet":
+        k = int(rng.integers(2, 8))
+        pool = _finite_bits(rng, name, k)
+        idx = _row_permuted(rng, np.tile(np.arange(L) % k, (R, 1)))  # every value as often as the others (L a multiple of k: all tied)
+        free = rng.random(R) < 0.5
+        idx[free] = rng.integers(0, k, size=(int(free.sum()), L))
+        bits = pool[idx]
+    elif cls == "constant":
+        bits = np.full((R, L), _finite_bits(rng, name, 1)[0], dtype=ut)
+    elif cls == "distinct":
+        span = int(_EXPONENT[name][0]) if name in FLOATS else 1 << (8 * DTYPE_BYTES[name])  # (floats: the non-negative finite patterns)
+        span = min(span, 1 << 62)
+        start = int(rng.integers(span))
+        bits = _row_permuted(rng, ((start + np.arange(L, dtype=np.int64)[None, :] + 7 * np.arange(R, dtype=np.int64)[:, None]) % span)).astype(ut)
+    elif cls == "hot":
+        bits = _finite_bits(rng, name, (R, L))
+        hot = _row_permuted(rng, np.tile(np.arange(L) < (L + 1) // 2, (R, 1)))
+        bits = np.where(hot, _finite_bits(rng, name, (R, 1)), bits)
+    elif cls == "row_edges":  # row r holds r % 100 and r % 100 + 1: its largest value is the next row's smallest, and that run is the longest
+        lo = (np.arange(R) % 100)[:, None]
+        a = rng.integers(L // 3, 2 * L // 3 + 1, size=(R, 1)) if L >= 2 else np.ones((R, 1), dtype=np.int64)
+        bits = _numbers_as_bits(_row_permuted(rng, np.where(np.arange(L)[None, :] < a, lo, lo + 1)), name)
+    elif cls == "specials":
+        pool = _special_pool(name)
+        bits = pool[rng.integers(0, pool.size, size=(R, L))]
+    elif cls == "thousand":
+        pool = _finite_bits(rng, name, 1000)
+        bits = pool[rng.integers(0, 1000, size=(R, L))]
+    elif cls == "uniform":
+        bits = _finite_bits(rng, name, (R, L))
+    else:
+        raise ValueError(f"unknown class {cls!r}")
+    return from_bits(np.ascontiguousarray(bits, dtype=ut).reshape(-1), name).reshape(moved).movedim(-1, dim).contiguous()
+
+
+def row_values(name: str, N: int, C: int, cls: str, consecutive: bool, seed: int):
+    """A contiguous [N, C] CPU tensor of rows of class `cls` (ROW_CLASSES, or "thousand"); consecutive: every row repeated a few times."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    ut = _BITS[DTYPE_BYTES[name]]
+    cols = np.arange(C)[None, :]
+
+    def alphabet(k):
+        return _finite_bits(rng, name, (C, k))[cols, rng.integers(0, k, size=(N, C))]
+
+    if cls == "few":
+        bits = alphabet(2)
+    elif cls == "thousand":
+        bits = alphabet(10)
+    elif cls == "equal":
+        bits = np.tile(_finite_bits(rng, name, (1, C)), (N, 1))
+    elif cls == "distinct":
+        bits = alphabet(2)
+        bits[:, 0] = _numbers_as_bits(rng.permutation(N) - N // 2, name)
+    elif cls == "sorted":
+        small = rng.integers(-1, 2, size=(N, C))
+        bits = _numbers_as_bits(small[np.lexsort(small.T[::-1])], name)
+    elif cls == "last_column":
+        bits = np.tile(_finite_bits(rng, name, (1, C)), (N, 1))
+        bits[:, -1] = _numbers_as_bits(rng.integers(-max(N // 4, 2), max(N // 4, 2), size=N), name)
+    elif cls == "behind_top":  # equal in the first 8 bytes, different behind them
+        top = 8 // DTYPE_BYTES[name]
+        bits = np.tile(_finite_bits(rng, name, (1, C)), (N, 1))
+        bits[:, top:] = alphabet(3)[:, top:]
+    elif cls == "specials":
+        pool = _special_pool(name)
+        bits = pool[rng.integers(0, pool.size, size=(N, C))]
+    else:
+        raise ValueError(f"unknown class {cls!r}")
+    if consecutive and cls not in ("equal", "distinct") and N:
+        bits = bits[np.minimum(np.cumsum(rng.random(N) < 0.4), N - 1)]
+    return from_bits(np.ascontiguousarray(bits, dtype=ut).reshape(-1), name).reshape(N, C)
+
+
+def _order_key_any(t):
+    """order_key, and an unsigned tensor's own bits (order_key is about signed integers and floats)."""
+    import torch
+    return to_bits(t) if t.dtype == torch.uint8 else order_key(t)
+
+
+def _neighbours_of(tests, name: str):
+    """Two values of the dtype `name`: just below the smallest and just above the largest of `tests` (as that dtype) in its order."""
+    key = _order_key_any(tests.to(torch_dtype(name)).reshape(-1))
+    top = int(np.iinfo(key.dtype).max)
+    pair = np.array([max(int(key.min()), 1) - 1, min(int(key.max()), top - 1) + 1], dtype=key.dtype)
+    return from_bits(pair, name) if name == "uint8" else values_of_key(pair, name)
+
+
+def third_inputs(case: dict) -> dict:
+    """name -> (base, view) as lay_out gives them, or a plain Python number: the inputs of a case of the third deck's ops, on the CPU."""
+    import torch
+    op, dtype, seed = case["op"], case["dtype"], case["data_seed"]
+    rng = np.random.Generator(np.random.PCG64(seed + 5))
+    out = {}
+    if op == "mode":
+        shape, dim = case["shape"], case["dim"]
+        out["x"] = lay_out(shape, case["layout"], lambda s: mode_values(dtype, s, dim, case["values"], seed))
+    elif op in ("unique_dim", "unique_consecutive_dim"):
+        dim = case["dim"] % len(case["shape"])
+
+        def rows(s):
+            rest = s[:dim] + s[dim + 1:]
+            return row_values(dtype, s[dim], _numel(rest), case["rows"], op == "unique_consecutive_dim", seed).reshape([s[dim]] + rest).movedim(0, dim).contiguous()
+
+        out["x"] = lay_out(case["shape"], case["layout"], rows)
+    elif op == "repeat_interleave":
+        rdt = torch_dtype(case["repeats_dtype"])
+        if case["rep_class"] == "equal":
+            repeats = {"zero_d": torch.tensor(case["k"], dtype=rdt), "one_element": torch.tensor([case["k"]], dtype=rdt), "int": case["k"]}[case["form"]]
+            out["repeats"] = repeats if case["form"] == "int" else (repeats, lambda t: t)
+        else:
+            r = torch.from_numpy(make_repeats(case["runs"], case["rep_class"], case["total_target"], case["rep_seed"])).to(rdt)
+            out["repeats"] = lay_out([case["runs"]], case["repeats_layout"], lambda s: r)
+        if case["form"] != "one_arg":
+            out["x"] = lay_out(case["shape"], case["layout"], lambda s: newer_values(dtype, s, case["dist"], seed))
+    else:  # isin
+        el, te = case["dtype"], case["test_dtype"]
+        m, q = _numel(case["test_shape"]), _numel(case["shape"])
+        tests = make_values(te, [m], case["test_dist"], seed)
+        if m and case["share"] != "none":  # duplicates: about a third of the test elements repeat another one
+            again = torch.from_numpy(rng.random(m) < 0.3)
+            tests = torch.where(again, tests[torch.from_numpy(rng.integers(0, m, size=m))], tests)
+        elements = make_values(el, [q], case["dist"], seed + 1)
+        if m and q and case["share"] != "none":
+            hits = tests[torch.from_numpy(rng.integers(0, m, size=q))].to(elements.dtype)
+            take = torch.ones(q, dtype=torch.bool) if case["share"] == "all" else torch.from_numpy(rng.random(q) < 0.5)
+            elements = torch.where(take, hits, elements)
+        if m and q >= 2 and case["share"] != "all":
+            elements[:2] = _neighbours_of(tests, el)
+        if case["signed_zero"] and m and q >= 3:
+            tests[0], elements[2] = 0.0, -0.0
+        if case["nans"] in ("tests", "both") and m >= 2 and te in FLOATS:
+            tests[1] = float("nan")
+        if case["nans"] in ("elements", "both") and q >= 4 and el in FLOATS:
+            elements[3] = float("nan")
+        as_number = lambda t: t.reshape(-1)[0].item()  # noqa: E731
+        out["elements"] = as_number(elements) if case["variant"] == "number_elements" else lay_out(case["shape"], case["layout"], lambda s: _fit(elements, s))
+        out["tests"] = as_number(tests) if case["variant"] == "number_tests" else lay_out(case["test_shape"], case["test_layout"], lambda s: _fit(tests, s))
+    return out
+
+
+def _fit(flat, shape):
+    """The first elements of a 1-D tensor as `shape` (an expanded layout asks for fewer than were made)."""
+    import torch
+    if flat.numel() < _numel(shape):  # (an empty shape expanded along its empty dimension: one element a row, none of them seen)
+        return torch.zeros(list(shape), dtype=flat.dtype)
+    return flat[:_numel(shape)].reshape(list(shape)).clone()
+
+
+def call_third(api, case: dict, t: dict):
+    """The one public call of a case of the third deck's ops on `api`: this library, or anything with the same functions."""
+    op = case["op"]
+    if op == "mode":
+        return api.mode(t["x"], case["dim"], case["keepdim"])
+    if op == "isin":
+        return api.isin(t["elements"], t["tests"], assume_unique=case["assume_unique"], invert=case["invert"])
+    if op == "repeat_interleave":
+        size = {"absent": None, "exact": case["total"], "too_large": case["total"] + case["extra"]}[case["output_size"]]
+        if case["form"] == "one_arg":
+            return api.repeat_interleave(t["repeats"], output_size=size)
+        return api.repeat_interleave(t["x"], t["repeats"], case["dim"], output_size=size)
+    fn = api.unique if op == "unique_dim" else api.unique_consecutive
+    return fn(t["x"], return_inverse=case["return_inverse"], return_counts=case["return_counts"], dim=case["dim"])
+
+
+# -- the third deck's references (torch's CPU functions and numpy only) ----------------------------------------------------------------
+
+def ref_mode(x, dim: int):
+    """The documented rule in numpy: per row along dim the smallest of the most frequent values, -0.0 and +0.0 one value and all NaNs one
+    value, the largest; the index of its LAST occurrence; the value with the bits of the element there.  -> (values, indices), dim kept."""
+    import torch
+    if x.dim() == 0:
+        return x.clone(), torch.zeros((), dtype=torch.int64)
+    rows = x.movedim(dim, -1).contiguous()
+    L = rows.shape[-1]
+    flat = rows.reshape(-1, L)
+    R = flat.shape[0]
+    canon = flat
+    if flat.dtype.is_floating_point:
+        canon = torch.where(torch.isnan(flat), torch.full((), float("nan"), dtype=flat.dtype), torch.where(flat == 0, torch.zeros((), dtype=flat.dtype), flat))
+    key = _order_key_any(canon)                  # (a positive quiet NaN: above +inf)
+    ks = np.sort(key, axis=1).reshape(-1)
+    heads = np.ones(R * L, dtype=bool)
+    heads[1:] = ks[1:] != ks[:-1]
+    heads[::L] = True                            # a run ends with its row
+    starts = np.flatnonzero(heads)
+    counts = np.diff(np.append(starts, R * L))
+    run_row = starts // L
+    first_run = np.flatnonzero(np.diff(run_row, prepend=-1))  # (every row has a run: L >= 1)
+    most = np.maximum.reduceat(counts, first_run)
+    cand = np.flatnonzero(counts == most[run_row])
+    _, first = np.unique(run_row[cand], return_index=True)  # the first of them: the smallest value
+    mode_key = ks[starts[cand[first]]]
+    last = L - 1 - np.argmax((key == mode_key[:, None])[:, ::-1], axis=1)
+    idx = torch.from_numpy(last.astype(np.int64)).reshape(-1, 1)
+    values = _signed_view(flat).gather(1, idx).view(flat.dtype)
+    shape = list(rows.shape[:-1]) + [1]
+    return values.reshape(shape).movedim(-1, dim), idx.reshape(shape).movedim(-1, dim)
+
+
+def ref_unique_rows(x, dim: int, consecutive: bool):
+    """unique(dim=) / unique_consecutive(dim=) on bit patterns: the slices along dim as rows of words, ordered word by word by the IEEE
+    total order (signed integers numerically), equal when bit-identical.  -> (values, inverse, counts)."""
+    import torch
+    rows = x.movedim(dim, 0).contiguous()
+    N = rows.shape[0]
+    flat = rows.reshape(N, -1)
+    key = order_key(flat)
+    order = np.arange(N) if consecutive else np.lexsort(key.T[::-1])  # (the first column decides first; stable)
+    ks = key[order]
+    heads = np.ones(N, dtype=bool)
+    heads[1:] = (ks[1:] != ks[:-1]).any(axis=1)
+    starts = np.flatnonzero(heads)
+    inverse = np.empty(N, dtype=np.int64)
+    inverse[order] = np.cumsum(heads) - 1
+    counts = np.diff(np.append(starts, N)).astype(np.int64)
+    values = rows[torch.from_numpy(order[starts])]
+    return values.movedim(0, dim), torch.from_numpy(inverse), torch.from_numpy(counts)
+
+
+def ref_isin(elements, tests, invert: bool):
+    """torch.isin on the CPU after torch's own promotion (float16 / bfloat16 as float32, which is exact).  assume_unique is not passed on:
+    the library documents that duplicates never change membership, and torch leaves the result open for them."""
+    import torch
+    common = torch.result_type(elements, tests)
+    e = elements.to(common) if isinstance(elements, torch.Tensor) else torch.tensor(elements, dtype=common)
+    t = tests.to(common) if isinstance(tests, torch.Tensor) else torch.tensor(tests, dtype=common)
+    if common in (torch.float16, torch.bfloat16):
+        e, t = e.float(), t.float()
+    return torch.isin(e.contiguous(), t.contiguous().reshape(-1), invert=invert)
+
+
+def ref_repeat_interleave(case: dict, cpu: dict):
+    """torch.repeat_interleave on the CPU; a too-large output_size: the documented answer, the last element repeated."""
+    import torch
+    total = None if case["output_size"] == "absent" else case["total"]
+    if case["form"] == "one_arg":
+        out, d = torch.repeat_interleave(cpu["repeats"].contiguous(), output_size=total), 0
+    else:
+        x = cpu["x"].contiguous()
+        rep = cpu["repeats"].contiguous() if isinstance(cpu["repeats"], torch.Tensor) else cpu["repeats"]
+        out = torch.repeat_interleave(x, rep, case["dim"], output_size=total)
+        d = 0 if case["dim"] is None else case["dim"] % max(x.dim(), 1)
+        last = (x.reshape(-1) if case["dim"] is None else x).narrow(d, (x.numel() if case["dim"] is None else x.shape[d]) - 1, 1) if case["extra"] else None
+    if case["extra"]:
+        if case["form"] == "one_arg":
+            last = torch.full((1,), case["runs"] - 1, dtype=out.dtype)
+        out = torch.cat((out, last.expand(*out.shape[:d], case["extra"], *out.shape[d + 1:])), dim=d)
+    return out
+
+
+def check_third(case: dict, cpu: dict, got: list) -> list:
+    import torch
+    op, bad = case["op"], []
+
+    def same(name, g, w):
+        line = _first_difference(name, g, w)
+        if line:
+            bad.append(line)
+
+    if op == "isin":
+        if len(got) != 1:
+            return [f"{len(got)} outputs returned, 1 expected"]
+        same("result", got[0], ref_isin(cpu["elements"], cpu["tests"], case["invert"]))
+    elif op == "repeat_interleave":
+        if len(got) != 1:
+            return [f"{len(got)} outputs returned, 1 expected"]
+        same("out", got[0], ref_repeat_interleave(case, cpu))
+    elif op == "mode":
+        if len(got) != 2:
+            return [f"{len(got)} outputs returned, 2 expected"]
+        x = cpu["x"]
+        dim = case["dim"] % max(x.dim(), 1)
+        values, indices = ref_mode(x, dim)
+        if not case["keepdim"] and x.dim():
+            values, indices = values.squeeze(dim), indices.squeeze(dim)
+        same("values", got[0], values)
+        same("indices", got[1], indices)
+        if not bad and not (x.dtype.is_floating_point and bool(torch.isnan(x).any())):  # torch's own values, where they are defined
+            exact = x.double() if x.dtype.is_floating_point else x.long()
+            theirs = torch.mode(exact, dim, case["keepdim"]).values if x.dim() else exact
+            if not bool((got[0].to(theirs.dtype) == theirs).all()):
+                at = int(torch.nonzero((got[0].to(theirs.dtype) != theirs).reshape(-1))[0])
+                bad.append(f"values against torch.mode: another value at flat {at}: returned {got[0].reshape(-1)[at].item()!r}, torch {theirs.reshape(-1)[at].item()!r}")
+    else:
+        x = cpu["x"]
+        dim = case["dim"] % x.dim()
+        want = ref_unique_rows(x, dim, op == "unique_consecutive_dim")
+        names = ["values"] + (["inverse"] if case["return_inverse"] else []) + (["counts"] if case["return_counts"] else [])
+        if len(got) != len(names):
+            return [f"{len(got)} outputs returned, {len(names)} expected"]
+        picked = {"values": want[0], "inverse": want[1], "counts": want[2]}
+        for name, g in zip(names, got):
+            same(name, g, picked[name])
+        if not bad and plain_values(x):
+            fn = torch.unique if op == "unique_dim" else torch.unique_consecutive
+            tw = _as_tuple(fn(x, return_inverse=case["return_inverse"], return_counts=case["return_counts"], dim=dim))
+            for name, g, w in zip(names, got, tw):
+                same(f"{name} against torch.{fn.__name__}(dim=)", g, w)
+    return bad
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # the runner
 
 class Mismatch(AssertionError):
@@ -1835,9 +2515,12 @@ def prepare(case: dict, device):
     stream.  A dependent searchsorted gets its queries only: its sequence is a library result that launch() picks up."""
     import torch
     op = case["op"]
-    if op in NEWER_OPS:
+    if op in NEWER_OPS or op in THIRD_OPS:
         cpu, gpu = {}, {}
-        for name, item in newer_inputs(case).items():
+        for name, item in (newer_inputs if op in NEWER_OPS else third_inputs)(case).items():
+            if not isinstance(item, tuple):  # (a Python number)
+                cpu[name] = gpu[name] = item
+                continue
             base, view = item
             cpu[name] = view(base)
             if device is not None:
@@ -1893,6 +2576,8 @@ def launch(case: dict, gpu: dict, results: dict):
     op = case["op"]
     if op in NEWER_OPS:
         return call_newer(vrs, case, gpu)
+    if op in THIRD_OPS:
+        return call_third(vrs, case, gpu)
     if case.get("variant") == "dependent":
         gpu["seq"] = results[case["source"]]  # what an earlier sort / unique of this window returned, possibly still being computed
     if op == "sort":
@@ -1928,6 +2613,8 @@ def check(case: dict, cpu: dict, result) -> list:
     got = [t.cpu() for t in _as_tuple(result)]
     if op in NEWER_OPS:
         return check_newer(case, cpu, got)
+    if op in THIRD_OPS:
+        return check_third(case, cpu, got)
     bad = []
 
     def same(name, g, w):
@@ -2095,7 +2782,7 @@ def main(argv) -> int:
     ap.add_argument("seconds", type=float, help="time budget of a soak (0 with --count)")
     ap.add_argument("seed", type=int)
     ap.add_argument("--count", type=int, default=None, help="run exactly the first COUNT cases instead of a time budget")
-    ap.add_argument("--deck", default="first", choices=["first", "newer"], help="which ops: the first deck's, or the newer ops among them")
+    ap.add_argument("--deck", default="first", choices=["first", "newer", "third"], help="which ops: the first deck's, the newer ops among them, or the third deck's")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)

@@ -137,9 +137,27 @@ int vrs_sort_rank_bytes(int dtype, int *rank_bytes);
  * ordered on the context's stream; the call only enqueues (after settling a pending one-call sort) -- except with VRS_TOPK_SORTED and
  * k > 4096, where the survivors are sorted by vrs_sort_segments_pairs_u32 (vrs_sort_segments_u32 without out_indices), which may wait
  * for the stream when its work lists grow; that sort's segments count in vrs_segmented_stats.
+ *
+ * TORCH'S ORDER: key_type VRS_TOPK_DTYPE(d), d a vrs_sort_dtype (I8, U8, I16, I32, I64, F16, BF16, F32, F64; another d:
+ * VRS_ERROR_INVALID_ARGUMENT).  keys holds num_elements elements of d IN THEIR OWN WIDTH (1, 2, 4 or 8 bytes) and a segment may begin
+ * at any element; out_keys holds num_segments * k elements of that width.  The rank is the one vrs_select_segments takes (torch.sort's:
+ * every NaN the largest, -0.0 equal to +0.0, signed integers by value; VRS_TOPK_LARGEST its complement, so NaNs come first), applied
+ * in registers as the elements are read; the result is what torch.sort(x, descending = largest, stable = True) puts first.
+ * out_keys[i*k + j] holds the selected element's OWN BITS, fetched from keys at its position -- a NaN keeps its payload and a zero its
+ * sign; slots [m, k) get all-ones bytes of the element's width (out_indices: 0xFFFFFFFF, as above), and bytes past num_segments * k *
+ * width are never written.  The selection reads the rank's significant bits in digits of at most 11 from the top: 1 / 2 / 3 / 6 levels
+ * for 8 / 16 / 32 / 64 bits.  The LDS tier holds 32 KB of ranks: 8192 elements of up to 4 bytes, 4096 of 8; the tier of a segment is
+ * vrs_select_tier_for(begin, end, num_elements, d, VRS_TUNE_TOPK_GRID_MIN_KEYS) -- vrs_topk_tier_for has no dtype and keeps its meaning
+ * for the three 32-bit key types (which it shares with every d of up to 4 bytes).  8-byte elements: flags must carry VRS_TOPK_RANK64
+ * (and no other key type may: VRS_ERROR_INVALID_ARGUMENT either way), the same bit vrs_topk_scratch_bytes sizes 8-byte ranks by, and
+ * keys and out_keys lie on 8-byte boundaries (VRS_ERROR_INVALID_ARGUMENT before anything is enqueued).  VRS_TOPK_SORTED with k > 4096
+ * sorts (rank, position) by vrs_sort_segments_pairs_u32, or vrs_sort_segments_pairs_u64 for 8-byte elements, with or without
+ * out_indices (without: the positions live in the scratch buffer), and fetches the own bits by position afterwards.  scratch: at most
+ * 4 n + 24 S k + 1 MiB with VRS_TOPK_RANK64.
  */
 typedef enum vrs_topk_key_type { VRS_TOPK_U32 = 0, VRS_TOPK_I32 = 1, VRS_TOPK_F32 = 2 } vrs_topk_key_type;
-enum { VRS_TOPK_LARGEST = 1, VRS_TOPK_SORTED = 2 }; /* flags */
+#define VRS_TOPK_DTYPE(d) (0x100 | (d)) /* key_type: an element of vrs_sort_dtype d, ranked in torch's order */
+enum { VRS_TOPK_LARGEST = 1, VRS_TOPK_SORTED = 2, VRS_TOPK_RANK64 = 16 }; /* flags */
 typedef enum vrs_topk_tier {
     VRS_TOPK_LDS = 0,   /* up to 8192 keys (empty segments included) */
     VRS_TOPK_BLOCK = 1, /* longer, below VRS_TUNE_TOPK_GRID_MIN_KEYS */
@@ -148,7 +166,8 @@ typedef enum vrs_topk_tier {
 int vrs_topk_segments(vrs_context ctx, vrs_buffer keys, uint32_t num_elements, vrs_buffer offsets, uint32_t num_segments,
                       uint32_t k, int key_type, int flags, vrs_buffer out_keys, vrs_buffer out_indices /* may be NULL */,
                       vrs_buffer scratch);
-/* the scratch vrs_topk_segments needs: a pure function, needs no device (0 for k == 0 or num_segments == 0) */
+/* the scratch vrs_topk_segments needs: a pure function, needs no device (0 for k == 0 or num_segments == 0).  flags: the call's;
+ * VRS_TOPK_RANK64 sizes the sort area for 8-byte ranks (never less than without it) */
 int vrs_topk_scratch_bytes(uint32_t num_elements, uint32_t num_segments, uint32_t k, int flags, uint64_t *bytes);
 /* the classification both the device and the tests use: a pure function, needs no device.  grid_min_keys: VRS_TUNE_TOPK_GRID_MIN_KEYS
  * (0 = never the grid tier); *tier = VRS_TOPK_*. */

@@ -10,7 +10,12 @@ against 8 TB/s.
 --crossover: rows of L keys (L from 16384 to 4M, R * L about 8.4e6, at least 1 row), each timed with VRS_TUNE_TOPK_GRID_MIN_KEYS = 1
 (every segment beyond the LDS tier takes the grid tier) and = 0 (the BLOCK tier): where the grid tier starts to win is the default.
 
-    python tools/topk_time.py [--cases abcde] [--reps 5] [--warmup 2] [--scale 1.0] [--crossover] [--out FILE]
+--dtypes: the torch.topk drop-in (vkradixsort_amd.torch_topk, largest, sorted) beside torch.topk and beside sort-then-slice
+(vkradixsort_amd.sort descending, then the first k): [1, 1e8] and [64, 131072] for bfloat16, float16, float32, int64 and float64,
+[100000, 1000] and [65536, 256] for bfloat16 and float32, k = 1, 8, 64, 1024 (those that fit the row).  Every timed call allocates its
+results and scratch inside.  The sort does not depend on k: timed once per shape and dtype.  No other table runs with --dtypes.
+
+    python tools/topk_time.py [--cases abcde] [--reps 5] [--warmup 2] [--scale 1.0] [--crossover] [--dtypes] [--out FILE]
 """
 from __future__ import annotations
 
@@ -55,6 +60,40 @@ def cases_for(name: str, scale: float):
     raise ValueError(name)
 
 
+def dtype_table(torch, vrs, dev, g, args) -> list:
+    """the torch.topk drop-in per dtype and shape: medians beside torch.topk and sort-then-slice"""
+    wide = [torch.bfloat16, torch.float16, torch.float32, torch.int64, torch.float64]
+    short = [torch.bfloat16, torch.float32]
+    big = max(int(1e8 * args.scale), 1)
+    shapes = [((1, big), wide), ((64, max(int(131072 * args.scale), 1)), wide), ((max(int(100000 * args.scale), 1), 1000), short),
+              ((max(int(65536 * args.scale), 1), 256), short)]
+    rows = []
+    for shape, dtypes in shapes:
+        for dtype in dtypes:
+            if dtype == torch.int64:
+                x = torch.randint(-(1 << 62), 1 << 62, shape, device=dev, generator=g, dtype=torch.int64)
+            else:
+                x = torch.randn(shape, device=dev, generator=g, dtype=torch.float32).to(dtype)
+            sort_ms = timed(torch, lambda: vrs.sort(x, dim=-1, descending=True), args.reps, args.warmup)["median_ms"]
+            for k in (1, 8, 64, 1024):
+                if k > shape[1]:
+                    continue
+                ours, theirs = vrs.torch_topk(x, k), torch.topk(x, k, dim=-1)
+                row = {"table": "dtypes", "dtype": str(dtype).replace("torch.", ""), "shape": list(shape), "k": k,
+                       "equals_torch_values": bool(torch.equal(ours.values, theirs.values)),
+                       "torch_topk_dropin_ms": timed(torch, lambda: vrs.torch_topk(x, k), args.reps, args.warmup)["median_ms"],
+                       "torch_topk_ms": timed(torch, lambda: torch.topk(x, k, dim=-1), args.reps, args.warmup)["median_ms"],
+                       "sort_then_slice_ms": sort_ms}
+                row["speedup_vs_torch_topk"] = row["torch_topk_ms"] / row["torch_topk_dropin_ms"]
+                row["speedup_vs_sort_then_slice"] = sort_ms / row["torch_topk_dropin_ms"]
+                row["read_share_of_8TBps"] = x.numel() * x.element_size() / (row["torch_topk_dropin_ms"] * 1e-3) / PEAK_BYTES_PER_S
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+            del x
+            torch.cuda.empty_cache()
+    return rows
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="abcde")
@@ -62,6 +101,7 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scale", type=float, default=1.0, help="sizes x scale (rehearsals)")
     ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--dtypes", action="store_true", help="the table of torch_topk per dtype and shape, and nothing else")
     ap.add_argument("--no-yardsticks", action="store_true", help="time the selection only (profiler runs)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "labs" / "topk_time.json"))
     args = ap.parse_args()
@@ -77,7 +117,9 @@ def main() -> int:
     ctx = context_for(dev)
     results = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "scale": args.scale,
                "grid_min_keys": capi.TOPK_GRID_MIN_KEYS_DEFAULT, "cases": []}
-    for name in args.cases:
+    if args.dtypes:
+        results["dtypes"] = dtype_table(torch, vrs, dev, g, args)
+    for name in "" if args.dtypes else args.cases:
         for label, shape, ks, dirs, distinct in cases_for(name, args.scale):
             if distinct:
                 x = (torch.randint(0, distinct, shape, device=dev, generator=g).float() * 0.5 - 1.0).contiguous()
@@ -107,7 +149,7 @@ def main() -> int:
                     results["cases"].append(row)
             del x, x2
             torch.cuda.empty_cache()
-    if args.crossover:
+    if args.crossover and not args.dtypes:
         sweep = []
         for L in [16384, 32768, 65536, 131072, 262144, 524288, 1 << 20, 1 << 22]:
             R = max(1, int((1 << 23) * args.scale) // L)

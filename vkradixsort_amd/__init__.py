@@ -4,7 +4,8 @@ csrc/    hand-written gfx950 HIP kernels + the C ABI (include/vkradixsort_amd*.h
 host/    C++ mirror of the reference's host classes (engine::GPUContext, Buffer, MultiRadixSortPass, ...)
 engine   the same interface for Python callers (tests, bench.py), a thin ctypes layer over the C ABI
 segmented  many independent segments sorted in one call (sort_segments over Buffers, sort_rows for 2-D torch tensors)
-topk       the k smallest / largest keys of every segment by radix select (topk_segments over Buffers, topk for torch tensors)
+topk       the k smallest / largest keys of every segment by radix select (topk_segments over Buffers, topk for torch tensors); the
+           torch.topk drop-in: nine dtypes, any dim and strides, torch's order, the elements' own bits (torch_topk)
 selection  torch.kthvalue / torch.median / torch.nanmedian drop-ins by a one-rank radix select: nine dtypes, any dim (select_segments over
            Buffers; kthvalue, median, nanmedian for torch tensors)
 quantile   torch.quantile / torch.nanquantile drop-ins by a multi-rank radix select: up to 16 order statistics per row carried through one
@@ -46,7 +47,7 @@ from .search import bucketize, isin, search_stats, searchsorted  # noqa: F401
 from .segmented import segmented_stats, sort_rows, sort_segments  # noqa: F401
 from .selection import kthvalue, median, nanmedian, select_scratch_bytes, select_segments, select_stats  # noqa: F401
 from .sort import argsort, sort, sort_values  # noqa: F401
-from .topk import topk, topk_segments, topk_stats  # noqa: F401
+from .topk import topk, topk_segments, topk_stats, torch_topk  # noqa: F401
 from .unique import run_length_encode, unique, unique_consecutive, unique_keys  # noqa: F401
 
 __version__ = "0.1.0"

@@ -84,6 +84,8 @@ TOPK_GRID_MIN_KEYS_DEFAULT = 1 << 17  # the library's default for VRS_TUNE_TOPK_
 # top-k selection: key types, flags, tiers (vrs_topk_tier) and the lengths that bound them
 VRS_TOPK_U32, VRS_TOPK_I32, VRS_TOPK_F32 = 0, 1, 2
 VRS_TOPK_LARGEST, VRS_TOPK_SORTED = 1, 2
+VRS_TOPK_RANK64 = 16  # goes with VRS_TOPK_DTYPE of int64 / float64: the scratch's sort area holds 8-byte ranks
+VRS_TOPK_DTYPE_BASE = 0x100
 VRS_TOPK_LDS, VRS_TOPK_BLOCK, VRS_TOPK_GRID = 0, 1, 2
 TOPK_LDS_MAX = 8192
 TOPK_SORT_IN_LDS_MAX_K = 4096  # VRS_TOPK_SORTED beyond this k sorts the survivors with vrs_sort_segments_pairs_u32
@@ -104,6 +106,11 @@ VRS_UNIQUE_U32, VRS_UNIQUE_I32, VRS_UNIQUE_F32, VRS_UNIQUE_U64, VRS_UNIQUE_I64, 
 VRS_UNIQUE_INVERSE, VRS_UNIQUE_COUNTS = 1, 2
 RLE_TILE = 4096
 VRS_UNIQUE_COLUMNS_SHIFT = 8
+
+
+def VRS_TOPK_DTYPE(d: int) -> int:
+    """The top-k key type of an element of dtype d (a VRS_SORT_* code), ranked in torch's order."""
+    return VRS_TOPK_DTYPE_BASE | d
 
 
 def VRS_UNIQUE_COLUMNS(c: int) -> int:
